@@ -15,7 +15,12 @@ every step. The trainer runs consecutive micro-batches of a window as ONE forwar
 window of 32 is cut 8 + 8 + 8 + 8; each micro-batch's loss is normalised by its own labelled rows - the reference's arithmetic,
 tests/test_trainer_gpu.py); steps and ms_per_step still count micro-batches. The line's config.micro_batches_per_pass says what ran.
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts its N ranks itself (self_launch). Weights are random-init at the exact
-Qwen3-4B / VGGT-1B / Perceiver shapes, inputs synthetic and already resident in HBM. Prints one JSON line on rank 0.
+Qwen3-4B / VGGT-1B / Perceiver shapes (drawn on the GPU from fixed seeds), inputs synthetic and already resident in HBM. Prints one JSON line
+on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and the line. Everything
+else it can measure - the trimmed-padding, schedule, forward-only, C4 / C5 and decode variants, the all-reduce timing, the live GEMM roofline
+and the CPU baseline - runs with --full (and its --no-* switches).
 """
 from __future__ import annotations
 
@@ -155,6 +160,47 @@ def cpu_baseline(model, batch, L):
                        % (agg.dino_depth, agg.depth, agg.depth, V, cfg.num_hidden_layers, L, float(loss.detach()), {k: round(v, 2) for k, v in t_all.items()}))}
 
 
+DUMP_SAMPLE = 1 << 21      # elements of each flat weight / optimiser-state buffer written by --dump-outputs (8 MB each in float32)
+
+
+def _fixed_sample(flat, seed):
+    """DUMP_SAMPLE elements of a flat device tensor at positions drawn from `seed` (the same positions whenever the size is the same)."""
+    n = flat.numel()
+    pos = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[pos.to(flat.device)]
+
+
+def timed_path_outputs(trainer, loss) -> dict:
+    """What the timed path hands its caller after its last step, as host float32 arrays: that micro-batch's loss, the pre-clip gradient
+    norm of the window's optimiser step, and the state that step left - the bf16 text weights, their fp32 master copy and Adam's first
+    moment at the same fixed sample of positions, and fixed samples of geom_head's fp32 parameters and, when it trains, the Perceiver's.
+    In dp_mode "sharded" every rank must call this (the optimiser state is all-gathered first)."""
+    trainer.gather_sharded_state()
+    gn = trainer.grad_norm()
+    out = {"loss": loss.detach().float().reshape(1),
+           "grad_norm": gn.float().reshape(1) if gn is not None else torch.full((1,), float("nan")),
+           "text_weights_sample": _fixed_sample(trainer.tm.flat_w, 0), "text_master_sample": _fixed_sample(trainer.master, 0),
+           "text_adam_m_sample": _fixed_sample(trainer.m, 0), "geom_master_sample": _fixed_sample(trainer.geom_master, 2)}
+    if trainer.proj_on:
+        out["projector_weights_sample"] = _fixed_sample(trainer.proj_w32, 1)
+    torch.cuda.synchronize()
+    return {k: v.detach().to("cpu", torch.float32).numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """arrays (name -> float32 / float64 numpy array) as out_dir/<name>.npy; refuses more than 64 MB in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed 64 MB")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def self_launch(n: int) -> int:
     """Runs this very command line under torch.distributed.run with n local ranks (rendezvous on 127.0.0.1, a free port) as a child
     process and returns its exit code. Replaces what the reference gets from `accelerate launch --config_file accelerate_8gpu.yaml`
@@ -196,6 +242,12 @@ def main():
     ap.add_argument("--vision-prefetch", action="store_true",
                     help="run the (frozen) vision tower one micro-batch ahead on a second stream (measured: no gain "
                          "on a saturated GPU; off by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also run the variants, the all-reduce timing, the GEMM roofline and the CPU baseline "
+                         "(each can be skipped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (loss, gradient norm, a fixed sample of the updated "
+                         "weights and optimiser state) as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-trim-variant", action="store_true", help="skip the second timed window (exact padding shortcut)")
     ap.add_argument("--no-variants", action="store_true",
@@ -248,7 +300,7 @@ def main():
     vcfg = VisionLanguageConfig(text_model_name="synthetic", vision_ckpt_dir="none", num_vis_tokens=128,
                                 geom_tokens=8 if args.geom else 0, projector_cfg=pcfg, text_config=qcfg,
                                 device=str(dev), seed=0, trim_padding=args.trim_pad, fp8_text_forward=args.fp8,
-                                train_projector=args.train_projector)
+                                train_projector=args.train_projector, init_on_device=True)
     model = VGGTQwen3VLM(vcfg)
     model.train()
     accum = args.grad_accum if args.grad_accum > 0 else max(1, min(32, args.steps))
@@ -323,12 +375,16 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
+    if args.dump_outputs:
+        outs = timed_path_outputs(trainer, loss)          # (a collective in dp_mode "sharded": every rank takes part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     # ---- the same K steps once more with the exact padding shortcut ("if the implementation skips padded
     # rows ... recompute the figure for the tokens actually executed and report both"). `value` above is the dense run;
     # this is reported beside it, never instead of it. Loss and gradients are identical (tests/test_fullsize_gpu.py).
     trimmed = None
-    if not args.trim_pad and not args.no_trim_variant:
+    if args.full and not args.trim_pad and not args.no_trim_variant:
         model.trim_padding = True
         loss_t = run_window(cycles[0])        # warm the trimmed shapes over one whole window
         sync()
@@ -373,13 +429,13 @@ def main():
     # Reported beside `value`, never instead of it. Every rank runs them (the collectives stay matched).
     sched_variants = {}
     comm = None
-    if use_dist:                                       # one more window of the headline schedule with events on the comm stream
+    if args.full and use_dist:                         # one more window of the headline schedule with events on the comm stream
         trainer.comm_profile = []
         run_window(cycles[0])
         torch.cuda.synchronize()
         comm = comm_summary(trainer.comm_profile, 1)
         trainer.comm_profile = None
-    if not args.no_variants and not args.trim_pad:
+    if args.full and not args.no_variants and not args.trim_pad:
         tg0 = trainer.text_group
         if tg0 > 1:
             trainer.set_schedule(text_group=1, grad_accum=accum)
@@ -429,7 +485,7 @@ def main():
     # Qwen3-4B forward"): the reference's unit is VGGTQwen3VLM.forward under no_grad / eval (vggt_qwen3_vlm.py:179-201)
     forward_only = None
     variants = {}
-    if world == 1 and not args.no_variants:
+    if args.full and world == 1 and not args.no_variants:
         def fwd():
             b = stream.pop()                     # a fresh micro-batch per forward (distinct inputs, new tensor objects)
             with torch.no_grad():
@@ -530,7 +586,7 @@ def main():
 
     # ---- live roofline of the dominant kernel (gemm_nt_kernel): one extra instrumented step, HIP events per launch
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         model.text_model._wgrad_stream = None   # serial launches: per-launch event times are not inflated by overlap
         row_split_env = os.environ.get("VQ3_VGGT_ROW_SPLIT")
         os.environ["VQ3_VGGT_ROW_SPLIT"] = "0"  # (likewise the tower's second stream: one chain per block while the events are in)
@@ -576,7 +632,7 @@ def main():
                 "traffic_unit": "bytes/launch (L2<->fabric, rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)",
                 "algorithmic_bytes_per_launch": round(by / nlaunch), "launches_per_step": round(nlaunch, 1), "avg_launch_us": round(ms * 1e3 / nlaunch, 2),
                 "gemm_ms_per_step": round(ms, 2), "gemm_tflop_per_step": round(fl / 1e12, 3)}
-    elif world > 1:
+    elif args.full and world > 1:
         nroof = max(1, min(int(getattr(model.text_model, "_wd_depth", 1)) * max(1, trainer.pass_size(accum)), accum))
         run_window(nroof)       # keep collectives matched across ranks
         run_window(nroof)
@@ -588,7 +644,7 @@ def main():
         out = {
             "metric": "Stage-1 train samples/sec (VGGT+Qwen3-4B bf16)", "value": round(value, 3), "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_executed": nwarm, "ms_per_step": round(ms_per_step, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp8-e4m3 fwd / bf16 bwd" if args.fp8 else "bf16", "data": "synthetic",
+            "higher_is_better": True, "full": bool(args.full), "scaling": "weak", "vs_baseline": None, "dtype": "fp8-e4m3 fwd / bf16 bwd" if args.fp8 else "bf16", "data": "synthetic",
             "config": {"workload": ("Stage-1 ScanQA bf16: VGGT-1B aggregator @%dpx x %d view(s) + 128-latent/6-layer "
                                     "Perceiver + Qwen3-4B fwd+bwd + RCCL all-reduce + AdamW(fp32 master); random-init "
                                     "weights; a step = one micro-batch of %d samples, run %d micro-batches per forward/backward pass "
@@ -612,7 +668,7 @@ def main():
         }
         out.update(sched_variants)
         out.update(variants)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(model, batch, L)
             except Exception as e:  # the baseline is reported-only; never lose the GPU line over it

@@ -161,7 +161,7 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     base = dict(os.environ, VQ3_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="2",
                 HSA_ENABLE_IPC_MODE_LEGACY="0", VQ3_GEMM_AUTOTUNE_LOG="1", VQ3_GEMM_TUNE_WS_MB="0")
     base.pop("VQ3_GEMM_TUNE_FILE", None)
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--layers", "2",
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--layers", "2", "--full",
            "--no-trim-variant", "--no-cpu-baseline"]
     procs = [subprocess.Popen(cmd, env=dict(base, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                               cwd=str(root), text=True) for r in range(2)]
@@ -208,7 +208,7 @@ def test_bench_one_rank_over_rccl():
     env = dict(os.environ, VQ3_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE="1", RANK="0",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("VQ3_DIST_BACKEND", None)
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--layers", "2",
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--layers", "2", "--full",
            "--no-trim-variant", "--no-cpu-baseline"]
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=str(root), text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
@@ -235,7 +235,7 @@ def test_bench_one_rank_over_rccl_sharded_mode():
     env = dict(os.environ, VQ3_FORCE_DIST="1", VQ3_DP_MODE="sharded", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE="1",
                RANK="0", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("VQ3_DIST_BACKEND", None)
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--layers", "2",
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--layers", "2", "--full",
            "--no-trim-variant", "--no-cpu-baseline", "--no-variants"]
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=str(root), text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
@@ -327,7 +327,7 @@ def test_bench_self_launch_two_ranks_gloo_on_one_gpu():
     env = dict(os.environ, VQ3_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", VQ3_GEMM_TUNE_WS_MB="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VQ3_GEMM_TUNE_FILE", "VQ3_FORCE_DIST"):
         env.pop(k, None)
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--layers", "2",
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--layers", "2", "--full",
            "--no-trim-variant", "--no-cpu-baseline", "--no-variants"]
     pr = subprocess.run(cmd, env=env, cwd=str(root), capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-3000:]

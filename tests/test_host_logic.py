@@ -440,3 +440,28 @@ def test_bench_self_launch_command_line(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and int(cmd[cmd.index("--master-port") + 1]) > 0
     assert cmd[-5:] == [str(root / "bench.py"), "--gpus", "4", "--steps", "8"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_options_and_dump_writer(tmp_path):
+    """bench.py: --full and --dump-outputs exist; dump_outputs writes each array as <name>.npy, round-trips float32 / float64 exactly,
+    and refuses another dtype or more than 64 MB in all."""
+    import importlib.util
+    import subprocess
+    import sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parents[1]
+    helptext = subprocess.run([sys.executable, str(root / "bench.py"), "--help"], capture_output=True, text=True, timeout=300).stdout
+    assert "--full" in helptext and "--dump-outputs" in helptext
+    spec = importlib.util.spec_from_file_location("vq3_bench_cpu", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    a = {"loss": np.array([12.5], np.float32), "w": np.linspace(-1, 1, 1000, dtype=np.float64)}
+    bench.dump_outputs(tmp_path / "out", a)
+    for k, v in a.items():
+        r = np.load(tmp_path / "out" / f"{k}.npy")
+        assert r.dtype == v.dtype and np.array_equal(r, v)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(tmp_path / "bad", {"ids": np.arange(4)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(tmp_path / "big", {"x": np.zeros(17 << 20, np.float32)})
+    assert not (tmp_path / "big").exists()

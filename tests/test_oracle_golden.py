@@ -79,10 +79,18 @@ def test_vlm_forward_matches_reference():
                        num_vis_tokens=m["num_vis_tokens"], geom_tokens=m["geom_tokens"], image_id=m["image_id"])
     assert relerr(out["vis_tokens"], torch.from_numpy(z["vis_tokens"])) < 1e-5
     assert relerr(out["features"][:, :m["geom_tokens"]], torch.from_numpy(z["geom_feats"])) < 1e-5
-    assert torch.equal(out["inputs_embeds"], bf16(z["inputs_embeds"]))
+    # The splice is exact: outside the geometry + visual span every row is the golden's bits, inside it every row is the bf16 image of
+    # the features this run computed. Those come from fp32 CPU matmuls whose summation order depends on the host (thread count, vector
+    # unit), so a few of them round to another bf16 value than the golden's (measured: 16 of 129024 values, 4.5e-5 over the tensor).
+    emb, emb_ref = out["inputs_embeds"], bf16(z["inputs_embeds"])
+    sm = ovlm.splice_srcmap(ids, m["num_vis_tokens"] + m["geom_tokens"], m["image_id"])
+    span = sm >= 0
+    rows = torch.arange(ids.shape[0])[:, None].expand_as(sm)
+    assert torch.equal(emb[~span], emb_ref[~span])
+    assert torch.equal(emb[span], out["features"].to(emb.dtype)[rows[span], sm[span].long()])
+    assert relerr(emb, emb_ref) < 3e-4
     assert abs(out["loss"].item() - float(z["loss"])) < 2e-3 * abs(float(z["loss"]))
     # integer image of the splice loop
-    sm = ovlm.splice_srcmap(ids, m["num_vis_tokens"] + m["geom_tokens"], m["image_id"])
     pos = (ids == m["image_id"]).nonzero()
     for b, p in pos.tolist():
         assert sm[b, p] == 0 and sm[b, p + m["num_vis_tokens"] + m["geom_tokens"] - 1] == m["num_vis_tokens"] + m["geom_tokens"] - 1

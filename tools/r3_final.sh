@@ -7,7 +7,7 @@ rm -rf $O; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1 && echo pytest gpu ok
 tail -n 3 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 && echo smoke ok
-VQ3_GEMM_TABLE=1 timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench.log 2> $O/bench.err && echo bench ok
+VQ3_GEMM_TABLE=1 timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.log 2> $O/bench.err && echo bench ok
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r3_final/bench.log').read().strip().splitlines()[-1])

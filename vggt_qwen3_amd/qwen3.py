@@ -96,7 +96,7 @@ class _Body(nn.Module):
 
 
 class Qwen3ForCausalLM(nn.Module):
-    def __init__(self, config: Qwen3Config, device="cuda", seed: Optional[int] = 0):
+    def __init__(self, config: Qwen3Config, device="cuda", seed: Optional[int] = 0, init_on_device: bool = False):
         super().__init__()
         self.config = config
         c = config
@@ -126,6 +126,7 @@ class Qwen3ForCausalLM(nn.Module):
         # fused causal attention (csrc/qwen_flash.hip) covers up to 4 query heads per kv head (Qwen3-4B: 4);
         # VQ3_QWEN_FLASH=0 keeps the batched GEMM + softmax chain
         self._flash = self.Hq % self.Hkv == 0 and self.Hq // self.Hkv <= 4 and os.environ.get("VQ3_QWEN_FLASH", "1") != "0"
+        self._init_on_device = init_on_device    # draw the random init with a generator on `device` instead of the host's
         self._alloc(c.vocab_size, seed)
         # weights written through load_state_dict() (any route) invalidate the e4m3 copies
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.refresh_derived())
@@ -160,14 +161,15 @@ class Qwen3ForCausalLM(nn.Module):
         self._g = {n: self.flat_g[o:o + math.prod(s)].view(s) for n, (o, s) in self.table.items()}
         self.vocab_p = round_up(vocab, 64)
         if seed is not None:
-            g = torch.Generator(device="cpu").manual_seed(seed)
+            gdev = dev if self._init_on_device else torch.device("cpu")
+            g = torch.Generator(device=gdev).manual_seed(seed)
             for n, w in self._w.items():
                 if w.dim() == 2:
-                    # chunked host-side normal init (std = initializer_range), like HF _init_weights
+                    # chunked normal init (std = initializer_range), like HF _init_weights; on the host unless init_on_device
                     rows = w.shape[0]
                     step = max(1, (1 << 24) // w.shape[1])
                     for r in range(0, rows, step):
-                        blk = torch.randn((min(step, rows - r), w.shape[1]), generator=g) * c.initializer_range
+                        blk = torch.randn((min(step, rows - r), w.shape[1]), generator=g, device=gdev) * c.initializer_range
                         w[r:r + blk.shape[0]].copy_(blk.to(BF16))
                 else:
                     w.fill_(1.0)

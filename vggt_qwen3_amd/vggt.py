@@ -45,7 +45,7 @@ def _block_param_shapes(C: int, mlp: int, qk_norm: bool) -> Dict[str, tuple]:
 class Aggregator(nn.Module):
     def __init__(self, img_size=518, patch_size=14, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4.0,
                  num_register_tokens=4, rope_freq=100.0, init_values=0.01, dino_depth: Optional[int] = None,
-                 device="cuda", seed: int = 0):
+                 device="cuda", seed: int = 0, init_on_device: bool = False):
         super().__init__()
         if embed_dim % 64 or embed_dim // num_heads != 64:
             raise ops._lib.Vq3Error("VGGT HIP path requires head_dim == 64")
@@ -60,7 +60,8 @@ class Aggregator(nn.Module):
         self.rope_freq = rope_freq
         self.kp = round_up(3 * patch_size * patch_size, 64)
         C = embed_dim
-        g = torch.Generator(device="cpu").manual_seed(seed)
+        gdev = torch.device(device) if init_on_device else torch.device("cpu")   # where the random init is drawn
+        g = torch.Generator(device=gdev).manual_seed(seed)
         shapes: Dict[str, tuple] = {}
         M = img_size // patch_size
         shapes["patch_embed.cls_token"] = (1, 1, C)
@@ -81,7 +82,7 @@ class Aggregator(nn.Module):
         shapes["register_token"] = (1, 2, num_register_tokens, C)
         self._names: List[str] = []
         for name, shp in shapes.items():
-            t = torch.empty(shp, dtype=F32)
+            t = torch.empty(shp, dtype=F32, device=gdev)
             leaf = name.split(".")[-1]
             if name in ("camera_token", "register_token", "patch_embed.cls_token", "patch_embed.register_tokens"):
                 t.normal_(0, 1e-6, generator=g)
@@ -395,11 +396,11 @@ class VGGT(nn.Module):
 
     def __init__(self, img_size=518, patch_size=14, embed_dim=1024, enable_camera=True, enable_point=True,
                  enable_depth=True, enable_track=True, depth=24, num_heads=None, dino_depth=None, device="cuda",
-                 seed: int = 0, **_unused):
+                 seed: int = 0, init_on_device: bool = False, **_unused):
         super().__init__()
         self.aggregator = Aggregator(img_size=img_size, patch_size=patch_size, embed_dim=embed_dim, depth=depth,
                                      num_heads=num_heads or embed_dim // 64, dino_depth=dino_depth, device=device,
-                                     seed=seed)
+                                     seed=seed, init_on_device=init_on_device)
         self.embed_dim = 2 * embed_dim
 
     def load_reference_state_dict(self, sd: Dict[str, torch.Tensor]) -> List[str]:

@@ -12,6 +12,7 @@ hand-written HIP backward of the whole text model (+ geom_head), so `accelerator
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 from pathlib import Path
@@ -50,6 +51,9 @@ class VisionLanguageConfig:
     # train_sft.py:138-145 gives it a learning-rate group. True = the "corrected" mode of SURVEY.md 3.1: the projector's forward saves
     # for backward, d(loss)/d(visual tokens) flows into its hand-written backward, the trainer updates it with proj_lr.
     train_projector: bool = False
+    # True: the random initial weights are drawn by seeded generators on `device` (milliseconds) instead of the host's (tens of seconds
+    # at full size, one CPU thread). Same distributions and seeds, different values; the default stays the host-side draw.
+    init_on_device: bool = False
 
 
 def build_srcmap(input_ids: torch.Tensor, image_id: int, S: int) -> torch.Tensor:
@@ -170,7 +174,8 @@ class VGGTQwen3VLM(nn.Module):
         self.device_ = dev
         # ---- text model + tokenizer (vggt_qwen3_vlm.py:31-42)
         if config.text_config is not None:
-            self.text_model = Qwen3ForCausalLM(config.text_config, device=dev, seed=config.seed)
+            self.text_model = Qwen3ForCausalLM(config.text_config, device=dev, seed=config.seed,
+                                               init_on_device=config.init_on_device)
             self.tokenizer = self._load_tokenizer(config.text_model_name, self.text_model.vocab)
         else:
             path = Path(config.text_model_name)
@@ -193,7 +198,7 @@ class VGGTQwen3VLM(nn.Module):
         # ---- projector + geom head (vggt_qwen3_vlm.py:46-56): fp32 parameters like the reference
         H = self.text_model.config.hidden_size
         g = torch.Generator().manual_seed(config.seed + 1)
-        with torch.random.fork_rng():
+        with torch.random.fork_rng(), (dev if config.init_on_device else contextlib.nullcontext()):
             torch.manual_seed(config.seed + 1)
             self.projector = PerceiverProjector(config.projector_cfg or PerceiverConfig(),
                                                 in_dim=self.vision_model.embed_dim, out_dim=H)
@@ -258,7 +263,7 @@ class VGGTQwen3VLM(nn.Module):
         from .vggt import VGGT
         kw = dict(img_size=518, patch_size=14, embed_dim=1024)
         kw.update(config.vision_config or {})
-        model = VGGT(device=self.device_, seed=config.seed + 2, **kw)
+        model = VGGT(device=self.device_, seed=config.seed + 2, init_on_device=config.init_on_device, **kw)
         ckpt = Path(config.vision_ckpt_dir) / "vggt_1B_commercial.pt"
         if ckpt.exists():
             sd = torch.load(ckpt, map_location="cpu")
