@@ -292,6 +292,43 @@ int vq3_perceiver_xattn_fwd(const void* q, const void* kv, void* o, void* P, voi
 int vq3_dropout(void* x, int32_t is_f32, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * LoRA adapters (peft tuners/lora/layer.py lora.Linear.forward: result = base_layer(x) + lora_B(lora_A(dropout(x))) * scaling)
+ * on the Qwen3 attention projections, and their backward. Up to VQ3_LORA_MAX_TARGETS targets share one launch; each is described by
+ * a HOST vq3_lora_target. The narrow operand W_t(j, k) / W_t(n, j) is bf16 at w[j * ldw + k] (w_kmajor = 0) or w[k * ldw + j]
+ * (w_kmajor = 1). Dropout: when p > 0 and the target's `mask` is set, element (m, c) of the masked operand is vq3_dropout's element
+ * mask_offset + m * mask_ld + c at `seed` (kept: bf16(x / (1 - p)); dropped: 0), applied in registers.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define VQ3_LORA_MAX_TARGETS 4
+typedef struct vq3_lora_target {
+  const void* w;
+  int64_t ldw;
+  int32_t w_kmajor;
+  int32_t mask;
+  int32_t x_col0, k;       /* down: X columns [x_col0, x_col0 + k) contracted; wgrad: R columns (nQ = k) */
+  int32_t y_col0, n;       /* up-add: Y columns [y_col0, y_col0 + n) written; wgrad: L columns (nP = n) */
+  int32_t u_col0;          /* down / up-add: the target's r columns of U start here; wgrad: its [n, k] block's offset in a slab row */
+  int32_t pad_;
+  uint64_t mask_offset;
+} vq3_lora_target;
+/* Down-projection, lora_A(dropout(x)) for every target at once (and, with W = lora_B stored k-major [n, r] and no mask, the backward's
+ * dV = dY . B): U[m, u_col0_t + j] = bf16(sum_k mask_t(X)[m, x_col0_t + k] . W_t(j, k)), j < r <= 64. X bf16 [M, ldx] is read once when
+ * every target contracts the same columns. U bf16 [M, ldu]. M >= 1 (decode rows included). */
+int vq3_lora_down(const void* X, int64_t ldx, int32_t M, const vq3_lora_target* targets, int32_t ntargets, int32_t r, void* U,
+                  int64_t ldu, float p, uint64_t seed, int64_t mask_ld, void* stream);
+/* Up-projection added in place, lora_B(...) * scaling: Y[m, y_col0_t + n] = bf16(Y + s * sum_t mask_t(m, y_col0_t + n) . sum_j
+ * U[m, u_col0_t + j] . W_t(n, j)), one rounding per element; columns no target covers are not written, and where the sum is zero Y keeps
+ * its bits. Targets may cover disjoint column blocks (forward: q | k | v of one fused projection) or the same one (backward:
+ * dX += sum_t mask_t o (s dV_t . A_t) with W = lora_A k-major); with M = out_features it is also the merge W += s B . A. */
+int vq3_lora_up_add(void* Y, int64_t ldy, int32_t M, const void* U, int64_t ldu, const vq3_lora_target* targets, int32_t ntargets,
+                    int32_t r, float s, float p, uint64_t seed, int64_t mask_ld, void* stream);
+/* Adapter weight gradients as f32 partial slabs over `slices` row ranges (no atomics): part[s * part_ld + u_col0_t + p * k_t + q] =
+ * alpha * sum_{m in slice s} L[m, y_col0_t + p] . mask_t(R)[m, x_col0_t + q] (dB = s dY^T . U, dA = dV^T . mask(X)); every slot of
+ * the targets' blocks is written. Sum the slab rows in order with vq3_colsum_f32 / vq3_colsum_f32_to_bf16. */
+int vq3_lora_wgrad_part(const void* L, int64_t ldl, const void* R, int64_t ldr, int32_t M, const vq3_lora_target* targets,
+                        int32_t ntargets, int32_t slices, float alpha, float p, uint64_t seed, int64_t mask_ld, float* part,
+                        int64_t part_ld, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser (src/train/train_sft.py:147-156 torch.optim.AdamW; DeepSpeed bf16 keeps f32 master weights)
  * ---------------------------------------------------------------------------------------------------------- */
 /* master/m/v f32, grad bf16, w_bf16 (compute copy) updated in place. step >= 1. grad is scaled by gscale first.

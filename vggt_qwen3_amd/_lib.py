@@ -57,6 +57,11 @@ class ColsumJob(C.Structure):
     _fields_ = [("part", c_p), ("out_bf16", c_p), ("nrows", i32), ("cols", i32), ("accumulate", i32)]
 
 
+class LoraTarget(C.Structure):
+    _fields_ = [("w", c_p), ("ldw", i64), ("w_kmajor", i32), ("mask", i32), ("x_col0", i32), ("k", i32), ("y_col0", i32), ("n", i32),
+                ("u_col0", i32), ("pad_", i32), ("mask_offset", C.c_uint64)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("src", c_p), ("h", i32), ("w", i32), ("pitch", i32), ("ksize_h", i32), ("ksize_v", i32),
                 ("kh_off", i32), ("kv_off", i32), ("bh_off", i32), ("bv_off", i32), ("crop_x", i32), ("crop_y", i32)]
@@ -139,6 +144,9 @@ SIGNATURES = {
     "vq3_gemm_split_poll": [c_p, i32],
     "vq3_gemm_split_debug_spin_bound": [i64],
     "vq3_pack_tokens": [c_p, c_p, c_p, c_p, i32, i32, i32, i64, c_p, c_p, c_p, c_p],
+    "vq3_lora_down": [c_p, i64, i32, C.POINTER(LoraTarget), i32, i32, c_p, i64, f32, C.c_uint64, i64, c_p],
+    "vq3_lora_up_add": [c_p, i64, i32, c_p, i64, C.POINTER(LoraTarget), i32, i32, f32, f32, C.c_uint64, i64, c_p],
+    "vq3_lora_wgrad_part": [c_p, i64, c_p, i64, i32, C.POINTER(LoraTarget), i32, i32, f32, f32, C.c_uint64, i64, c_p, i64, c_p],
 }
 _RESTYPES = {"vq3_last_error": C.c_char_p, "vq3_target_arch": C.c_char_p, "vq3_qwen_decode_layers_workspace_bytes": i64}
 

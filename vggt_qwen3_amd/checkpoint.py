@@ -169,7 +169,7 @@ def save_trainer_state(trainer, out_dir) -> Path:
     out = Path(out_dir)
     out.mkdir(parents=True, exist_ok=True)
     st = {"micro": trainer.micro, "opt_step": trainer.opt_step, "grad_accum": trainer.grad_accum,
-          "layout": {k: [int(o), list(s)] for k, (o, s) in trainer.tm.table.items()},
+          "layout": _state_layout(trainer),
           "master": trainer.master.cpu(), "m": trainer.m.cpu(), "v": trainer.v.cpu(),
           "geom_master": trainer.geom_master.cpu(), "geom_m": trainer.geom_m.cpu(), "geom_v": trainer.geom_v.cpu()}
     if getattr(trainer, "proj_on", False):       # trained projector ("corrected" mode): its fp32 parameters live in the model file
@@ -178,9 +178,18 @@ def save_trainer_state(trainer, out_dir) -> Path:
     return out / TRAINER_STATE
 
 
+def _state_layout(trainer) -> dict:
+    """The flat layout the master / moment vectors follow: the text model's, or the LoRA adapters' (with their settings)."""
+    lo = getattr(trainer, "lora", None)
+    if lo is not None:
+        return {"lora": {k: [int(o), list(s)] for k, (o, s) in lo.table.items()},
+                "lora_settings": [lo.s.r, lo.s.alpha, lo.s.dropout, list(lo.s.target_modules)]}
+    return {k: [int(o), list(s)] for k, (o, s) in trainer.tm.table.items()}
+
+
 def load_trainer_state(trainer, ckpt_dir) -> None:
     st = torch.load(Path(ckpt_dir) / TRAINER_STATE, map_location="cpu", weights_only=True)
-    layout = {k: [int(o), list(s)] for k, (o, s) in trainer.tm.table.items()}
+    layout = _state_layout(trainer)
     if st["layout"] != layout:
         raise RuntimeError("trainer state was written for a different flat parameter layout")
     if st["micro"] % trainer.grad_accum:
@@ -191,10 +200,64 @@ def load_trainer_state(trainer, ckpt_dir) -> None:
     if getattr(trainer, "proj_on", False) and "proj_m" in st:
         trainer.proj_m.copy_(st["proj_m"]); trainer.proj_v.copy_(st["proj_v"])
     from . import ops
-    trainer.tm.flat_w.copy_(ops.cast(trainer.master, torch.bfloat16))
-    trainer.tm.refresh_derived()      # e4m3 / W^T copies follow the restored weights (they were built at construction)
+    if getattr(trainer, "lora", None) is not None:
+        trainer.lora.sync_compute_copy()      # the adapters' masters were restored; the frozen base is the model file's
+    else:
+        trainer.tm.flat_w.copy_(ops.cast(trainer.master, torch.bfloat16))
+        trainer.tm.refresh_derived()      # e4m3 / W^T copies follow the restored weights (they were built at construction)
     off = 0
     with torch.no_grad():
         for p in trainer.geom_params:
             p.copy_(trainer.geom_master[off:off + p.numel()].view_as(p))
             off += p.numel()
+
+
+def _text_model(model):
+    return model.text_model if hasattr(model, "text_model") else model
+
+
+def save_lora_adapter(model, out_dir) -> Path:
+    """peft's on-disk adapter (PeftModel.save_pretrained): adapter_config.json + adapter_model.safetensors with the fp32 adapter
+    masters under base_model.model.model.layers.{i}.self_attn.{q,k,v,o}_proj.lora_{A,B}.weight. `model`: the VLM or its text model."""
+    from safetensors.torch import save_file
+    from .lora import adapter_config, peft_key
+    tm = _text_model(model)
+    lo = tm.lora
+    if lo is None:
+        raise RuntimeError("save_lora_adapter: the model has no LoRA adapters (enable_lora)")
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    tensors = {peft_key(i, t, w): lo.tensor(lo.master, i, t, w).detach().cpu().contiguous() for i, t, w in lo.named()}
+    save_file(tensors, str(out / "adapter_model.safetensors"))
+    (out / "adapter_config.json").write_text(json.dumps(adapter_config(lo.s), indent=2))
+    return out
+
+
+def load_lora_adapter(model, ckpt_dir, seed: int = 0) -> None:
+    """Inverse of save_lora_adapter: enables adapters with the saved config when the model has none, then copies every tensor into the
+    fp32 masters and the bf16 compute copy. A config that differs from the model's adapters, or a missing key, raises."""
+    from safetensors.torch import load_file
+    from .lora import peft_key, validate
+    tm = _text_model(model)
+    path = Path(ckpt_dir)
+    cfg = json.loads((path / "adapter_config.json").read_text())
+    if cfg.get("peft_type", "LORA") != "LORA" or cfg.get("use_dora") or cfg.get("use_rslora") or cfg.get("bias", "none") != "none":
+        raise NotImplementedError(f"load_lora_adapter: unsupported adapter config {cfg}")
+    want = validate(cfg["r"], cfg["lora_alpha"], cfg.get("lora_dropout", 0.0), cfg["target_modules"])
+    if tm.lora is None:
+        model.enable_lora(r=want.r, alpha=want.alpha, dropout=want.dropout, target_modules=want.target_modules, seed=seed)
+        tm = _text_model(model)
+    lo = tm.lora
+    if (lo.s.r, lo.s.alpha, list(lo.s.target_modules)) != (want.r, want.alpha, list(want.target_modules)):
+        raise ValueError(f"load_lora_adapter: saved adapters {want} do not match the model's {lo.s}")
+    sd = load_file(str(path / "adapter_model.safetensors"))
+    with torch.no_grad():
+        for i, t, w in lo.named():
+            k = peft_key(i, t, w)
+            if k not in sd:
+                raise KeyError(f"load_lora_adapter: {k} missing from {path}")
+            dst = lo.tensor(lo.master, i, t, w)
+            if tuple(sd[k].shape) != tuple(dst.shape):
+                raise ValueError(f"load_lora_adapter: {k} has shape {tuple(sd[k].shape)}, the model wants {tuple(dst.shape)}")
+            dst.copy_(sd[k].to(torch.float32))
+    lo.sync_compute_copy()

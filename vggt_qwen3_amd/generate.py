@@ -72,7 +72,7 @@ class DecodeState:
         # B = 1 at Qwen3-4B's shape: all decoder layers of a step in ONE persistent launch (csrc/decode_layers.hip) instead of six
         # launches per layer; every other case decodes with one launch per projection
         self.persistent = None
-        if (B == 1 and getattr(tm, "_fp8", None) is None and os.environ.get("VQ3_DECODE_PERSISTENT", "1") != "0"
+        if (B == 1 and getattr(tm, "_fp8", None) is None and not tm.lora_frozen and os.environ.get("VQ3_DECODE_PERSISTENT", "1") != "0"
                 and ops.decode_layers_supported(c.hidden_size, c.intermediate_size, tm.Hq, tm.Hkv, tm.D, Lmax)):
             names = ("qkv", "o", "gu", "down", "ln1", "ln2", "qn", "kn")
             assert all(tm._w[f"l{i}.{n}"].is_contiguous() for i in range(nl) for n in names)
@@ -134,12 +134,17 @@ def _decode_step(tm, st: DecodeState, cos, sin, opts) -> None:
             return ops.skinny_linear_fp8(x, wq, ws, **kw)
         return ops.skinny_linear(x, tm._w[name], **kw)
 
+    lo = tm.lora if tm.lora_frozen else None                        # unmerged LoRA adapters: their terms after q|k|v and o
     for i in range(c.num_hidden_layers):
         qkv = proj(h, f"l{i}.qkv", ln_w=tm._w[f"l{i}.ln1"], eps=c.rms_norm_eps)
+        if lo is not None and lo.attn:
+            lo.fwd_qkv(i, ops.rmsnorm_fwd(h, tm._w[f"l{i}.ln1"], c.rms_norm_eps), qkv, training=False)
         Q = ops.qwen_decode_qkprep(qkv, tm._w[f"l{i}.qn"], tm._w[f"l{i}.kn"], cos, sin, st.lens, st.K[i], st.V[i], B, Hq, Hkv,
                                    D, st.Lmax, c.rms_norm_eps)
         ao = ops.qwen_decode_attn(Q, st.K[i], st.V[i], st.lens, B, Hq, Hkv, D, st.Lmax, D ** -0.5)
         h_mid = proj(ao, f"l{i}.o", residual=h)
+        if lo is not None:
+            lo.fwd_o(i, ao, h_mid, training=False)
         gu = proj(h_mid, f"l{i}.gu", ln_w=tm._w[f"l{i}.ln2"], eps=c.rms_norm_eps)
         h = proj(gu, f"l{i}.down", residual=h_mid, swiglu=True)
     _logits_and_pick(tm, st, h, opts)

@@ -1022,3 +1022,82 @@ def gemm_split_debug_spin_bound(polls: int = 0) -> None:
 def gemm_force_config(cfg: int = -3) -> None:
     """Force vq3_gemm_bf16_nt's tile configuration for NT shapes (-3 = automatic). Benchmarks and tests only."""
     check(_lib.load().vq3_gemm_force_config(cfg), "vq3_gemm_force_config")
+
+
+# ----------------------------------------------------------------------------------------------- LoRA (csrc/lora.hip)
+LORA_MAX_TARGETS = 4     # include/vq3_hip.h: VQ3_LORA_MAX_TARGETS
+
+
+def _lora_targets(targets):
+    """targets: dicts with the vq3_lora_target fields (w: a bf16 tensor view; ldw defaults to its row stride)."""
+    if not 1 <= len(targets) <= LORA_MAX_TARGETS:
+        raise _lib.Vq3Error(f"lora: 1..{LORA_MAX_TARGETS} targets per launch, got {len(targets)}")
+    arr = (_lib.LoraTarget * len(targets))()
+    for a, t in zip(arr, targets):
+        w = t.get("w")                    # (the weight gradients take no narrow operand)
+        if w is not None:
+            _req(w, BF16, "lora operand")
+            assert w.dim() == 2 and w.stride(1) == 1
+        a.w, a.ldw = (0, 1) if w is None else (w.data_ptr(), int(t.get("ldw", w.stride(0))))
+        a.w_kmajor, a.mask = int(t.get("kmajor", 0)), int(t.get("mask", 0))
+        a.x_col0, a.k, a.y_col0, a.n = int(t.get("x_col0", 0)), int(t.get("k", 0)), int(t.get("y_col0", 0)), int(t.get("n", 0))
+        a.u_col0, a.mask_offset = int(t.get("u_col0", 0)), int(t.get("mask_offset", 0)) & (2 ** 64 - 1)
+    return arr
+
+
+def lora_down(X: torch.Tensor, targets, r: int, U: Optional[torch.Tensor] = None, ucols: Optional[int] = None, p: float = 0.0,
+              seed: int = 0, mask_ld: Optional[int] = None) -> torch.Tensor:
+    """U[m, u_col0_t + j] = sum_k mask_t(X)[m, x_col0_t + k] . W_t(j, k) (vq3_lora_down): lora_A(dropout(x)) of every target at once,
+    or dV = dY . B with W = lora_B k-major. X bf16 [M, *] with unit column stride; U bf16 [M, ucols]."""
+    _req(X, BF16, "lora_down X")
+    assert X.dim() == 2 and X.stride(1) == 1
+    M = X.shape[0]
+    if U is None:
+        U = torch.empty((M, ucols if ucols is not None else len(targets) * r), device=X.device, dtype=BF16)
+    _req(U, BF16, "lora_down U")
+    assert U.dim() == 2 and U.stride(1) == 1 and U.shape[0] == M
+    arr = _lora_targets(targets)
+    check(_lib.load().vq3_lora_down(X.data_ptr(), X.stride(0), M, arr, len(targets), r, U.data_ptr(), U.stride(0), float(p),
+                                    seed & (2 ** 64 - 1), X.shape[1] if mask_ld is None else mask_ld, _stream()), "vq3_lora_down")
+    return U
+
+
+def lora_up_add(Y: torch.Tensor, U: torch.Tensor, targets, r: int, s: float, p: float = 0.0, seed: int = 0,
+                mask_ld: Optional[int] = None) -> torch.Tensor:
+    """Y[m, y_col0_t + n] = bf16(Y + s * sum_t mask_t . sum_j U[m, u_col0_t + j] . W_t(n, j)) in place (vq3_lora_up_add)."""
+    _req(Y, BF16, "lora_up_add Y"); _req(U, BF16, "lora_up_add U")
+    assert Y.dim() == 2 and Y.stride(1) == 1 and U.dim() == 2 and U.stride(1) == 1 and U.shape[0] == Y.shape[0]
+    arr = _lora_targets(targets)
+    check(_lib.load().vq3_lora_up_add(Y.data_ptr(), Y.stride(0), Y.shape[0], U.data_ptr(), U.stride(0), arr, len(targets), r, float(s),
+                                      float(p), seed & (2 ** 64 - 1), Y.shape[1] if mask_ld is None else mask_ld, _stream()),
+          "vq3_lora_up_add")
+    return Y
+
+
+def lora_wgrad(L: torch.Tensor, R: torch.Tensor, targets, out: torch.Tensor, alpha: float = 1.0, accumulate: bool = False,
+               p: float = 0.0, seed: int = 0, mask_ld: Optional[int] = None, slices: Optional[int] = None) -> torch.Tensor:
+    """out[u_col0_t + p' * k_t + q] (+)= alpha * sum_m L[m, y_col0_t + p'] . mask_t(R)[m, x_col0_t + q] over every row m: f32 partial
+    slabs per row slice (vq3_lora_wgrad_part), summed in slice order (vq3_colsum_f32 / _to_bf16). out: f32 or bf16, 1-D."""
+    _req(L, BF16, "lora_wgrad L"); _req(R, BF16, "lora_wgrad R")
+    assert L.dim() == 2 and R.dim() == 2 and L.stride(1) == 1 and R.stride(1) == 1 and L.shape[0] == R.shape[0]
+    assert out.dim() == 1 and out.is_contiguous() and out.dtype in (F32, BF16)
+    M = L.shape[0]
+    width = out.numel()
+    if slices is None:
+        tiles = sum(max(1, t["n"] * t["k"] // 4096) for t in targets)
+        slices = max(1, min((M + 15) // 16, (1024 + tiles - 1) // tiles))
+    part = torch.empty((slices, width), device=L.device, dtype=F32)
+    arr = _lora_targets(targets)
+    lib = _lib.load()
+    check(lib.vq3_lora_wgrad_part(L.data_ptr(), L.stride(0), R.data_ptr(), R.stride(0), M, arr, len(targets), slices, float(alpha), float(p),
+                                  seed & (2 ** 64 - 1), R.shape[1] if mask_ld is None else mask_ld, part.data_ptr(), width, _stream()),
+          "vq3_lora_wgrad_part")
+    # (slots outside the targets' blocks hold garbage in `part`; the column sum covers only what the targets own)
+    lo = min(t.get("u_col0", 0) for t in targets)
+    hi = max(t.get("u_col0", 0) + t["n"] * t["k"] for t in targets)
+    pv = part[:, lo:hi]
+    if lo != 0 or hi != width:
+        pv = pv.contiguous()
+    fn = lib.vq3_colsum_f32 if out.dtype == F32 else lib.vq3_colsum_f32_to_bf16
+    check(fn(pv.data_ptr(), slices, hi - lo, out[lo:hi].data_ptr(), 1 if accumulate else 0, _stream()), "lora_wgrad colsum")
+    return out

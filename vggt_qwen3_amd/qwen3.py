@@ -127,6 +127,7 @@ class Qwen3ForCausalLM(nn.Module):
         # VQ3_QWEN_FLASH=0 keeps the batched GEMM + softmax chain
         self._flash = self.Hq % self.Hkv == 0 and self.Hq // self.Hkv <= 4 and os.environ.get("VQ3_QWEN_FLASH", "1") != "0"
         self._init_on_device = init_on_device    # draw the random init with a generator on `device` instead of the host's
+        self.lora = None                          # LoRA adapters (enable_lora); the base is frozen while they are active
         self._alloc(c.vocab_size, seed)
         # weights written through load_state_dict() (any route) invalidate the e4m3 copies
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.refresh_derived())
@@ -240,13 +241,99 @@ class Qwen3ForCausalLM(nn.Module):
         self.grad_views = self._grad_views()
 
     def publish_grads(self):
-        """Expose the flat gradient buffer through the parameters' .grad (for stock torch optimisers / DDP)."""
+        """Expose the flat gradient buffer through the parameters' .grad (for stock torch optimisers / DDP). With active LoRA adapters
+        only the adapters have gradients: their .grad are views of the flat adapter gradient."""
         named = dict(self.named_parameters())
+        if self.lora_frozen:
+            for n, g in self.lora_grad_views().items():
+                named[n].grad = g
+            return
         for n, g in self.grad_views.items():
             named[n].grad = g
 
     def zero_grad_flat(self):
+        if self.lora_frozen:
+            self.lora.zero_grad()
+            return
         self.flat_g.zero_()
+
+    def grad_anchor(self):
+        """(a trainable parameter, the buffer view its .grad is while it is live): how the autograd route tells a fresh window
+        (overwrite) from one whose gradients accumulate."""
+        if self.lora_frozen:
+            from .lora import runtime_name
+            i, t, w = next(self.lora.named())
+            n = runtime_name(i, t, w)
+            return dict(self.named_parameters())[n], self.lora_grad_views()[n]
+        return next(iter(self.parameters())), self.grad_views["model.embed_tokens.weight"]
+
+    def trainable_grad_buffer(self) -> torch.Tensor:
+        """The flat gradient of what trains: flat_g, or the adapters' gradient while they are active."""
+        return self.lora.g if self.lora_frozen else self.flat_g
+
+    # ------------------------------------------------------------------ LoRA (vggt_qwen3_amd/lora.py)
+    @property
+    def lora_frozen(self) -> bool:
+        """Active adapters: the base is frozen and only they train."""
+        return self.lora is not None and self.lora.active
+
+    def enable_lora(self, r: int = 8, alpha: float = 8.0, dropout: float = 0.0, target_modules=("q_proj", "v_proj"), seed: int = 0):
+        """peft.get_peft_model(self, LoraConfig(r, lora_alpha=alpha, lora_dropout=dropout, target_modules=...)) on the attention
+        projections of every layer: adapters named as peft's (model.layers.{i}.self_attn.q_proj.lora_A.default.weight, ...), every base
+        parameter frozen (requires_grad False)."""
+        from .lora import LoraAdapters, runtime_name, validate
+        st = validate(r, alpha, dropout, target_modules)
+        if getattr(self, "_fp8", None) is not None:
+            raise NotImplementedError("LoRA with the fp8 forward (config C5) is not implemented")
+        if self.lora is not None:
+            raise RuntimeError("enable_lora: adapters already exist (several named adapters are not supported)")
+        if "o_proj" in st.target_modules and not self._flash:
+            raise NotImplementedError("LoRA on o_proj needs the fused causal attention (up to 4 query heads per kv head, VQ3_QWEN_FLASH on)")
+        if any(self._wd_rows):
+            self.flush_deferred()
+        self._pass_weights_gate()
+        self.lora = lo = LoraAdapters(self, st, seed=seed)
+        for p in self.parameters():
+            p.requires_grad_(False)
+        layers = self.model.layers
+        for i, t, which in lo.named():
+            proj = getattr(layers[i].self_attn, t)
+            key = f"lora_{which}"
+            if not hasattr(proj, key):
+                setattr(proj, key, nn.ModuleDict())
+            getattr(proj, key)["default"] = _W(lo.tensor(lo.master, i, t, which))     # fp32 masters, as peft keeps them
+            assert runtime_name(i, t, which) in dict(self.named_parameters())
+        return lo
+
+    def lora_grad_views(self) -> Dict[str, torch.Tensor]:
+        from .lora import runtime_name
+        lo = self.lora
+        return {runtime_name(i, t, w): lo.tensor(lo.g, i, t, w) for i, t, w in lo.named()}
+
+    def lora_parameters(self):
+        named = dict(self.named_parameters())
+        from .lora import runtime_name
+        return [named[runtime_name(i, t, w)] for i, t, w in self.lora.named()]
+
+    def merge_lora(self) -> None:
+        """W += (alpha / r) B . A into the base weights (peft's merge_and_unload), then the derived copies follow and the adapters turn
+        off: every route (decode kernels included) then runs the merged weights unchanged."""
+        if self.lora is None or not self.lora.active:
+            raise RuntimeError("merge_lora: no active adapters")
+        self._pass_weights_gate()
+        lo = self.lora
+        lo.merge_into(self)
+        # peft's merge_and_unload: the adapter modules leave (state_dict / save_model carry plain HF keys) and the base trains again
+        layers = self.model.layers
+        for i, t, which in lo.named():
+            proj = getattr(layers[i].self_attn, t)
+            if hasattr(proj, f"lora_{which}"):
+                delattr(proj, f"lora_{which}")
+        lo.active = False
+        self.lora = None
+        for p in self.parameters():
+            p.requires_grad_(True)
+        self.refresh_derived()
 
     # ------------------------------------------------------------------ HF-compatible surface
     def get_input_embeddings(self):
@@ -325,6 +412,8 @@ class Qwen3ForCausalLM(nn.Module):
         its rows are quantised (vq3_quant_fp8_rows_scaled). Embedding / lm_head, norms, attention and the weight-gradient GEMMs stay
         bf16 (they read the saved bf16 activations and bf16 dY)."""
         self._pass_weights_gate()                 # (quantises the weights: an optimiser step on the trainer's side stream must be complete)
+        if on and self.lora_frozen:
+            raise NotImplementedError("the fp8 forward (config C5) with unmerged LoRA adapters is not implemented")
         self._fp8 = {} if on else None
         if dgrad is None:
             dgrad = os.environ.get("VQ3_FP8_DGRAD", "1") != "0"
@@ -395,6 +484,10 @@ class Qwen3ForCausalLM(nn.Module):
         Hq, Hkv, D, G = self.Hq, self.Hkv, self.D, self.Hq // self.Hkv
         cos, sin = self.rope(L)
         qkv = self._proj(xn, f"l{i}.qkv")
+        if self.lora_frozen:
+            lst = self.lora.fwd_qkv(i, xn, qkv, self.training)
+            if ctx is not None:
+                ctx["lora_qkv"] = lst
         Q, K, V, qr, kr = ops.qwen_qkprep_fwd(qkv, self._w[f"l{i}.qn"], self._w[f"l{i}.kn"], cos, sin, B, L, Hq, Hkv,
                                               D, c.rms_norm_eps, want_rstd=ctx is not None)
         if self._flash:
@@ -444,13 +537,20 @@ class Qwen3ForCausalLM(nn.Module):
         # dominates and ONE workgroup per live key tile wins (133.7 against 132.4 samples/s): no split, and no host read to decide it)
         h = inputs_embeds.reshape(B * L, H)
         saved: List[dict] = []
-        wd_off = self._wd_begin(B * L) if save else None       # row offset of this micro-batch in the deferred-wgrad slabs (or None)
+        if self.lora_frozen:
+            self.lora.refresh_compute_copy()
+        # row offset of this micro-batch in the deferred-wgrad slabs (or None; a frozen base has no weight gradients to defer)
+        wd_off = self._wd_begin(B * L) if save and not self.lora_frozen else None
         wv = (lambda i, key: self._wd_view(i, key, wd_off, B * L)) if wd_off is not None else (lambda i, key: None)
         for i in range(c.num_hidden_layers):
             ctx = {} if save else None
             xn1, r1 = ops.rmsnorm_fwd(h, self._w[f"l{i}.ln1"], c.rms_norm_eps, want_rstd=True, out=wv(i, "qkv.X"))
             ao = self._attention_fwd(i, xn1, B, L, keymask, ctx, ao_out=wv(i, "o.X"))
             h_mid = self._proj(ao, f"l{i}.o", residual=h)
+            if self.lora_frozen:
+                lst = self.lora.fwd_o(i, ao, h_mid, self.training)
+                if save:
+                    ctx["lora_o"] = lst
             xn2, r2 = ops.rmsnorm_fwd(h_mid, self._w[f"l{i}.ln2"], c.rms_norm_eps, want_rstd=True, out=wv(i, "gu.X"))
             if getattr(self, "_fp8", None) is None and ops.swiglu_fwd_fusable(B * L, c.intermediate_size, H):
                 # gate|up projection with silu(gate) * up in its epilogue: act leaves with gu, no second pass over [rows, 2 I]
@@ -618,7 +718,9 @@ class Qwen3ForCausalLM(nn.Module):
     def _wgrad(self, name: str, dY: torch.Tensor, X: torch.Tensor, accumulate: bool, slab: bool = False):
         """dW[N,K] (+)= dY^T[N,M] . X[M,K]: dY and X are read as stored (k-major A and B operands, contraction = token
         rows). Weight gradients have no consumer inside the backward, so they are enqueued on a second HIP stream:
-        their GEMM tails overlap the dgrad chain on the main one."""
+        their GEMM tails overlap the dgrad chain on the main one. A frozen base (active LoRA adapters) has none."""
+        if self.lora_frozen:
+            return
         side = self._wgrad_stream
         if side is None:
             self._wgrad_now(name, dY, X, accumulate)
@@ -737,6 +839,8 @@ class Qwen3ForCausalLM(nn.Module):
             Wo = self._w[f"l{i}.o"]
             if self._flash:
                 d_ao = self._dgrad(dh_mid, f"l{i}.o")                   # token-major [B*L, Hq*D]: one plain GEMM
+                if self.lora_frozen:
+                    self.lora.bwd_o(i, ctx.get("lora_o"), dh_mid, ctx["ao"], d_ao, accumulate)
                 if wd_off is None:
                     self._wgrad(f"l{i}.o", dh_mid, ctx["ao"], accumulate)
                 dQ, dK, dV = ops.qwen_flash_bwd(ctx["Q"], ctx["K"], ctx["V"], saved["keymask"], ctx["ao"], d_ao, ctx["lse"],
@@ -752,6 +856,8 @@ class Qwen3ForCausalLM(nn.Module):
                                        ctx["qr"], ctx["kr"], self._g[f"l{i}.qn"], self._g[f"l{i}.kn"], accumulate, B, L,
                                        self.Hq, self.Hkv, D, defer=norm_jobs, out=wv(i, "qkv.dY"))
             d_xn1 = self._dgrad(dqkv, f"l{i}.qkv")
+            if self.lora_frozen:
+                self.lora.bwd_qkv(i, ctx.get("lora_qkv"), dqkv, ctx["xn1"], d_xn1, accumulate)
             if wd_off is None:
                 self._wgrad(f"l{i}.qkv", dqkv, ctx["xn1"], accumulate)
             else:
@@ -763,7 +869,10 @@ class Qwen3ForCausalLM(nn.Module):
                     self._wd_rows[i] = wd_off[i] + M
             dh = ops.rmsnorm_bwd(d_xn1, ctx["h_in"], self._w[f"l{i}.ln1"], ctx["r1"], dh_mid, self._g[f"l{i}.ln1"],
                                  accumulate, defer=norm_jobs, out=wv(i - 1, "down.dY") if (wd_off is not None and i > 0) else None)
-            ops.colsum_flush(norm_jobs)
+            if self.lora_frozen:
+                norm_jobs.clear()            # a frozen base has no norm-weight gradients: the column sums are not run
+            else:
+                ops.colsum_flush(norm_jobs)
             if layer_done is not None:
                 self.join_wgrad_stream()
                 layer_done(i)
@@ -811,10 +920,13 @@ class Qwen3ForCausalLM(nn.Module):
             d_hn32 = torch.zeros((n8, H), device=dev, dtype=F32)
             ops.gemm_raw(dlog, E, d_hn32, n8, H, Vp, Vp, H, H, alpha=gscale, transB=True, ksplit=max(2, 256 // ntile))
         d_hn = ops.cast(d_hn32, BF16)
-        # dE[Vp, H] (+)= dlogits^T[Vp, n8] . hn[n8, H]    (both k-major; contraction = the n8 selected rows)
-        ops.gemm_raw(dlog, head_ctx["hn"], dE, Vp, H, n8, Vp, H, H, accumulate=accumulate, alpha=gscale, transA=True,
-                     transB=True)
-        d_hs = ops.rmsnorm_bwd(d_hn, head_ctx["hs"], self._w["norm"], head_ctx["rstd"], None, self._g["norm"], accumulate)
+        # dE[Vp, H] (+)= dlogits^T[Vp, n8] . hn[n8, H]    (both k-major; contraction = the n8 selected rows; none for a frozen base)
+        frozen = self.lora_frozen
+        if not frozen:
+            ops.gemm_raw(dlog, head_ctx["hn"], dE, Vp, H, n8, Vp, H, H, accumulate=accumulate, alpha=gscale, transA=True,
+                         transB=True)
+        d_hs = ops.rmsnorm_bwd(d_hn, head_ctx["hs"], self._w["norm"], head_ctx["rstd"], None, self._g["norm"], accumulate,
+                               defer=[] if frozen else None)          # (a frozen final norm: its weight-gradient sum is dropped)
         dh = torch.zeros((rows, H), device=dev, dtype=BF16)
         ops.scatter_rows(d_hs, head_ctx["idx"], dh, n, False)
         return dh

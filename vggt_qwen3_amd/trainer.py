@@ -67,6 +67,11 @@ class Stage1Trainer:
         # "allreduce" (default): SUM all-reduce of every bucket, replicated AdamW. "sharded" (opt-in, dp.py): reduce-scatter of every
         # bucket from inside the backward, clipping + AdamW on this rank's 1/world of each bucket, all-gather of the updated weights
         self.dp_mode = dp_mode or os.environ.get("VQ3_DP_MODE", "allreduce")
+        # LoRA adapters (text_model.enable_lora): the base is frozen; AdamW, clipping and the gradient exchange cover the adapters
+        self.lora = self.tm.lora if self.tm.lora_frozen else None
+        if self.lora is not None and self.dp_mode == "sharded":
+            raise NotImplementedError("Stage1Trainer: dp_mode='sharded' with LoRA adapters is not implemented (their state is a few MB: "
+                                      "use the default 'allreduce')")
         if self.dp_mode not in ("allreduce", "sharded"):
             raise ValueError(f"dp_mode must be 'allreduce' or 'sharded', got {self.dp_mode!r}")
         # (one rank: nothing to shard - unless VQ3_FORCE_DIST asks for the collectives themselves, the one-rank RCCL rehearsal of
@@ -109,9 +114,14 @@ class Stage1Trainer:
         self.micro = 0       # micro-batches seen (the reference's `step`)
         self.opt_step = 0    # optimiser / scheduler steps
         dev = self.tm.flat_w.device
-        n = self.tm.flat_w.numel()
-        # fp32 master weights + Adam moments for the text model (flat) and geom_head (small, flat)
-        self.master = ops.cast(self.tm.flat_w, F32)
+        # fp32 master weights + Adam moments for the text model (flat) and geom_head (small, flat). With LoRA adapters the masters are
+        # the adapters' own (LoraAdapters.master) and flat_w has none: the frozen base is never updated
+        if self.lora is not None:
+            n = self.lora.numel
+            self.master = self.lora.master
+        else:
+            n = self.tm.flat_w.numel()
+            self.master = ops.cast(self.tm.flat_w, F32)
         self.m = torch.zeros(n, device=dev, dtype=F32)
         self.v = torch.zeros(n, device=dev, dtype=F32)
         self.geom_params = [p for _, p in model.geom_head.named_parameters()]
@@ -130,8 +140,11 @@ class Stage1Trainer:
         self.last_grad_norm = None      # device scalar of the last optimiser step (pre-clip), for logging / tests
         # all-reduce buckets over flat_g: groups of `bucket_layers` layers (contiguous), norm with the last group,
         # the tied embedding last (its gradient is completed by the embedding backward at the very end)
-        self.buckets, self.embed_span = dp.plan_buckets(self.tm.table, self.tm.config.num_hidden_layers, bucket_layers)
-        dp.check_cover(self.buckets, self.embed_span, n)
+        if self.lora is not None:
+            self.buckets, self.embed_span = {}, None            # the adapters' gradient is ONE all-reduce after the window's backward
+        else:
+            self.buckets, self.embed_span = dp.plan_buckets(self.tm.table, self.tm.config.num_hidden_layers, bucket_layers)
+            dp.check_cover(self.buckets, self.embed_span, n)
         self.comm_stream = torch.cuda.Stream(device=dev) if self.dist_on else None
         # "corrected" mode (VisionLanguageConfig.train_projector): the Perceiver's fp32 parameters, gradients and Adam moments as flat
         # buffers (the parameters and their .grad become views), one gradient all-reduce bucket of their own, the proj_lr group
@@ -194,7 +207,8 @@ class Stage1Trainer:
         """The bf16 weights were replaced behind the trainer's back (a checkpoint load): re-derive the fp32 master copy, or
         the next AdamW step would write the old weights back. Adam moments are kept."""
         self.sync_optimizer()
-        self.master.copy_(ops.cast(self.tm.flat_w, F32))
+        if self.lora is None:
+            self.master.copy_(ops.cast(self.tm.flat_w, F32))
         off = 0
         for p in self.geom_params:
             self.geom_master[off:off + p.numel()].copy_(p.detach().reshape(-1).float())
@@ -381,6 +395,8 @@ class Stage1Trainer:
     def _optimizer_step_impl(self):
         tm = self.tm
         self.check_kernels()                 # before the weights are touched
+        if self.lora is not None:
+            return self._lora_step()
         if self.dist_on:
             for g0 in sorted(self.buckets, reverse=True):     # buckets the backward did not reach (no hook fired)
                 if g0 not in self._fired:
@@ -442,6 +458,55 @@ class Stage1Trainer:
                            self.betas[1], self.eps, self.wd, self.opt_step, gscale, clip=clip)
             self.model.projector._cc = None               # bf16 compute copies are rebuilt from the updated fp32 parameters
         tm.refresh_derived()     # e4m3 / W^T copies of the weights (no-ops unless enabled)
+        if geom_step:
+            ops.adamw_step(self.geom_master, self.geom_m, self.geom_v, ops.cast(self.geom_grad[: self._gn].contiguous(), BF16),
+                           self.geom_w16, self.proj_lr * mult, self.betas[0], self.betas[1], self.eps, self.wd,
+                           self.opt_step, gscale, clip=clip)
+            off = 0
+            with torch.no_grad():
+                for p in self.geom_params:
+                    p.copy_(self.geom_master[off:off + p.numel()].view_as(p))
+                    off += p.numel()
+
+    def _lora_step(self):
+        """The optimiser step with LoRA adapters: one all-reduce of the flat adapter gradient (a few MB) plus geom_head / projector,
+        the global-norm clip over adapters, projector and geom_head, AdamW on the adapters' fp32 masters (their bf16 compute copy is
+        written by the same kernel) in the `lr` group. No W^T refresh or e4m3 requantisation: the base never changes."""
+        lo = self.lora
+        if self.dist_on:
+            self.comm_stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self.comm_stream):
+                dp.allreduce_tensor(lo.g, group=self.pg)
+                if self.geom_on:
+                    dp.allreduce_tensor(self.geom_grad, group=self.pg)
+            torch.cuda.current_stream().wait_stream(self.comm_stream)
+        proj_g16 = None
+        if self.proj_on:
+            proj_g16 = ops.cast(self.proj_g32, BF16)
+            if self.dist_on:
+                dp.allreduce_tensor(proj_g16, group=self.pg)
+        self.opt_step += 1
+        mult = self.lr_mult(self.opt_step)
+        gscale = 1.0 / self.world
+        geom_step = self.geom_on and float(self.geom_grad[self._gn].item()) > 0
+        g16 = ops.cast(lo.g, BF16)           # adapter gradients leave as bf16 like the base's (vq3_adamw_step's operand)
+        clip = None
+        if self.max_grad_norm is not None and self.max_grad_norm > 0:
+            self.norm_sq.zero_()
+            ops.sumsq(g16, self.norm_part, self.norm_sq)
+            if geom_step:
+                ops.sumsq(self.geom_grad[: self._gn], self.norm_part, self.norm_sq)
+            if proj_g16 is not None:
+                ops.sumsq(proj_g16, self.norm_part, self.norm_sq)
+            clip = (self.norm_sq, float(self.max_grad_norm))
+            self.last_grad_norm = self.norm_sq.sqrt() * gscale
+        ops.adamw_step(lo.master, self.m, self.v, g16, lo.w, self.lr * mult, self.betas[0], self.betas[1], self.eps, self.wd,
+                       self.opt_step, gscale, clip=clip)
+        lo._synced = lo.master._version          # (the kernel wrote the compute copy itself)
+        if proj_g16 is not None:
+            ops.adamw_step(self.proj_w32, self.proj_m, self.proj_v, proj_g16, self.proj_w16, self.proj_lr * mult, self.betas[0],
+                           self.betas[1], self.eps, self.wd, self.opt_step, gscale, clip=clip)
+            self.model.projector._cc = None
         if geom_step:
             ops.adamw_step(self.geom_master, self.geom_m, self.geom_v, ops.cast(self.geom_grad[: self._gn].contiguous(), BF16),
                            self.geom_w16, self.proj_lr * mult, self.betas[0], self.betas[1], self.eps, self.wd,

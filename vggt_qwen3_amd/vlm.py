@@ -25,6 +25,7 @@ from . import ops
 from .hostplan import PLAN
 from .ops import BF16, F32
 from .perceiver import PerceiverConfig, PerceiverProjector
+from .lora import lora_settings_from_stage_config  # noqa: F401  (the reference's `lora:` block)
 from .qwen3 import Qwen3Config, Qwen3ForCausalLM
 
 GEOM_FEATURE_DIM = 37  # R(9) + t(3) + K(9) + depth_hist(16)   (vggt_qwen3_vlm.py:51)
@@ -124,8 +125,8 @@ class _TextLossFn(torch.autograd.Function):
         # them and the HIP backward accumulates in place, exactly when .grad is still our view from an earlier backward
         # (optimizer.zero_grad(set_to_none=True) drops the views -> the next backward overwrites; set_to_none=False zeroes
         # the buffer through the views -> accumulation into zeros).
-        first = next(iter(tm.parameters()))
-        live = first.grad is not None and first.grad.data_ptr() == tm.grad_views["model.embed_tokens.weight"].data_ptr()
+        first, anchor = tm.grad_anchor()
+        live = first.grad is not None and first.grad.data_ptr() == anchor.data_ptr()
         d_geom = model._backward_text(st, gscale, accumulate=live)
         tm.publish_grads()
         return (None, None, d_geom if ctx.has_geom else None, *([None] * len(model._text_param_names)))
@@ -151,18 +152,19 @@ class _TextLossFn(torch.autograd.Function):
                 "that DistributedDataParallel's reducer never sees - replicas would diverge silently. Use vggt_qwen3_amd.trainer.Stage1Trainer "
                 "(bucketed RCCL all-reduce inside the backward), or set model.autograd_dp = 'allreduce' (this route reduces the flat gradient "
                 "itself; not available with train_projector=True) / 'local' (you reduce text_model.flat_g yourself)." % world)
-        first = next(iter(tm.parameters()))
-        live = first.grad is not None and first.grad.data_ptr() == tm.grad_views["model.embed_tokens.weight"].data_ptr()
+        first, anchor = tm.grad_anchor()
+        live = first.grad is not None and first.grad.data_ptr() == anchor.data_ptr()
+        gbuf = tm.trainable_grad_buffer()                       # flat_g, or the adapters' gradient while LoRA is active
         if mode == "local":
             d_geom = model._backward_text(st, gscale, accumulate=live)
         else:
-            keep = tm.flat_g.clone() if live else None          # what earlier backwards of the window accumulated (already reduced)
+            keep = gbuf.clone() if live else None               # what earlier backwards of the window accumulated (already reduced)
             d_geom = model._backward_text(st, gscale, accumulate=False)
             torch.cuda.current_stream().synchronize()
-            dp.allreduce_tensor(tm.flat_g, group=group)         # every rank comes here once per backward, labelled rows or not
-            tm.flat_g.mul_(1.0 / world)
+            dp.allreduce_tensor(gbuf, group=group)              # every rank comes here once per backward, labelled rows or not
+            gbuf.mul_(1.0 / world)
             if keep is not None:
-                tm.flat_g.add_(keep)
+                gbuf.add_(keep)
         tm.publish_grads()
         return (None, None, d_geom if ctx.has_geom else None, *([None] * len(model._text_param_names)))
 
@@ -233,6 +235,20 @@ class VGGTQwen3VLM(nn.Module):
         # _TextLossFn._backward_multi_rank. "allreduce" | "raise" | "local"; the process group is `autograd_dp_group` (None = WORLD)
         self.autograd_dp = os.environ.get("VQ3_AUTOGRAD_DP", "allreduce")
         self.autograd_dp_group = None
+
+    # ------------------------------------------------------------------ LoRA (vggt_qwen3_amd/lora.py)
+    def enable_lora(self, r: int = 8, alpha: float = 8.0, dropout: float = 0.0, target_modules=("q_proj", "v_proj"), seed: int = 0):
+        """peft.get_peft_model(text_model, LoraConfig(...)) as the reference's stage configs ask for it (lora_settings_from_stage_config):
+        adapters on the text model's attention projections, named under text_model as peft names them; the text model's base parameters
+        are frozen. The projector and geom_head keep their treatment, the vision tower stays frozen."""
+        lo = self.text_model.enable_lora(r=r, alpha=alpha, dropout=dropout, target_modules=target_modules, seed=seed)
+        self._text_param_names = [n for n, _ in self.text_model.named_parameters()]
+        self._graphs = {}                # captured eval graphs ran the weights without the adapters
+        return lo
+
+    def merge_lora(self) -> None:
+        self.text_model.merge_lora()
+        self._graphs = {}
 
     def _autograd_dp_world(self):
         import torch.distributed as dist
@@ -573,9 +589,12 @@ class VGGTQwen3VLM(nn.Module):
         if st["geom_ctx"] is not None or st.get("pctx") is not None:
             dfeat = torch.zeros((B, S, H), device=d_emb.device, dtype=F32)
         live = st.get("live")
-        if live is None or os.environ.get("VQ3_EMBED_BWD_LIVE", "1") == "0":
+        dtable = None if tm.lora_frozen else tm._g["embed"]      # a frozen base (LoRA adapters) has no embedding gradient
+        if dtable is None and dfeat is None:
+            pass
+        elif live is None or os.environ.get("VQ3_EMBED_BWD_LIVE", "1") == "0":
             sorted_ids, order = torch.sort(ids, stable=True)
-            ops.embed_splice_bwd(sorted_ids, order, st["srcmap"], d_emb, tm._g["embed"], dfeat, B, L, H, S)
+            ops.embed_splice_bwd(sorted_ids, order, st["srcmap"], d_emb, dtable, dfeat, B, L, H, S)
         else:
             # Rows that cannot carry a gradient leave the id runs (index plumbing, no arithmetic): each gets a sort key of its own
             # behind every real id - a run of one, marked "skip" in the table pass's source map - so the run of the padding id, which
@@ -586,7 +605,8 @@ class VGGTQwen3VLM(nn.Module):
             keys = torch.where(live, ids, pos + (1 << 40))
             sorted_keys, order = torch.sort(keys, stable=True)
             srcmap_tbl = torch.where(live, st["srcmap"].reshape(-1), torch.zeros_like(st["srcmap"].reshape(-1)))
-            ops.embed_splice_bwd(sorted_keys, order, srcmap_tbl, d_emb, tm._g["embed"], None, B, L, H, S)
+            if dtable is not None:
+                ops.embed_splice_bwd(sorted_keys, order, srcmap_tbl, d_emb, dtable, None, B, L, H, S)
             if dfeat is not None:
                 ops.embed_splice_bwd(sorted_keys, order, st["srcmap"], d_emb, None, dfeat, B, L, H, S)
         if dfeat is None:
@@ -638,6 +658,8 @@ class VGGTQwen3VLM(nn.Module):
             return st["loss"]
         self._last_state = st
         params = [p for _, p in self.text_model.named_parameters()]
+        if len(params) != len(self._text_param_names):
+            self._text_param_names = [n for n, _ in self.text_model.named_parameters()]
         geom_in = None
         if st["geom_ctx"] is not None:
             geom_in = _GeomBridge.apply(self, st, *[self.geom_head[0].weight, self.geom_head[0].bias,
