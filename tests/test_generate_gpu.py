@@ -403,12 +403,12 @@ def test_persistent_decode_layer_stage_by_stage(ops):
     assert rel(h, h_out)[0] <= 1.5e-2
 
 
-@pytest.mark.parametrize("L", [21, 125, 300, 520])
+@pytest.mark.parametrize("L", [21, 125, 300, 520, 1400, 2039])
 def test_persistent_decode_generate_matches_full_forward(L):
     """generate() on the persistent route (B = 1, Qwen3-4B's shape, graph replay): the logits behind each greedy pick equal those of a
     cache-free forward over prompt + generated tokens within the bf16 tie tolerance - the test the per-projection route passes above.
     Prompt lengths on both sides of the attention's 128-row chunks: one chunk, the 128 boundary crossed while decoding, three chunks
-    (the double-buffered loop's second trip), five."""
+    (the double-buffered loop's second trip), five; a long prompt, and one whose cache grows to exactly DL_LMAX = 2048 rows."""
     from vggt_qwen3_amd import ops
     if not ops.decode_layers_supported(2560, 9728, 32, 8, 128, 128):
         pytest.skip("needs an MI355X (256 CUs)")
@@ -424,6 +424,87 @@ def test_persistent_decode_generate_matches_full_forward(L):
     for t in range(9):
         row = logits[:, L - 1 + t]
         assert ((row.max(-1).values - row.gather(1, out[:, t][:, None]).squeeze(1)) < TIE_TOL).all(), t
+
+
+def _full_forward_logits(tm, emb_row, new_ids):
+    """Logits of a cache-free forward over one row's prompt embeddings followed by its generated ids (all but the last)."""
+    full = torch.cat([emb_row[None], tm.get_input_embeddings()(new_ids[None, :-1])], dim=1)
+    h, _ = tm.forward_hidden(full, torch.ones(1, full.shape[1], dtype=torch.long).cuda(), save=False)
+    return tm.logits_all(h).view(h.shape[0], -1).float()           # (rows past the sequence: forward_hidden's padding, unused)
+
+
+def test_decode_past_the_persistent_cache_limit_takes_the_per_projection_route():
+    """A prompt of 2100 tokens needs Lmax = 2112 > DL_LMAX = 2048: generate() decodes with one launch per projection (stats say so)
+    and still matches the full forward under the tie rule."""
+    from vggt_qwen3_amd import ops
+    if not ops.decode_layers_supported(2560, 9728, 32, 8, 128, 128):
+        pytest.skip("needs an MI355X (256 CUs)")
+    tm, cfg = _qwen4b_dims(2)
+    torch.manual_seed(8)
+    L, NEW = 2100, 9
+    emb = (torch.randn(1, L, cfg.hidden_size) * 0.5).to(BF16).cuda()
+    out, stats = tm.generate(inputs_embeds=emb, attention_mask=torch.ones(1, L, dtype=torch.long).cuda(), max_new_tokens=NEW,
+                             use_graph=True, return_stats=True)
+    assert stats["Lmax"] == 2112 and stats["persistent"] is False and out.shape == (1, NEW)
+    logits = _full_forward_logits(tm, emb[0], out[0])
+    for t in range(NEW):
+        row = logits[L - 1 + t]
+        assert row.max() - row[out[0, t]] < TIE_TOL, t
+
+
+def test_persistent_decode_attention_at_2040_positions_vs_fp64(ops):
+    """The persistent kernel's attention output row (workspace w_attn) after a 2040-token prefill, Lmax = 2048 = DL_LMAX, against an
+    fp64 softmax attention of the same query (qkprep of the kernel's own q|k|v row) over the 2041 cache rows the kernel left."""
+    from vggt_qwen3_amd import generate as G
+    if not ops.decode_layers_supported(2560, 9728, 32, 8, 128, 2048):
+        pytest.skip("needs an MI355X (256 CUs)")
+    tm, cfg = _qwen4b_dims(1)
+    torch.manual_seed(6)
+    L0, Lmax = 2040, 2048
+    emb = (torch.randn(1, L0, cfg.hidden_size) * 0.5).to(BF16).cuda()
+    cos, sin = tm.rope(Lmax)
+    st = G.DecodeState(tm, 1, Lmax, 8)
+    assert st.persistent is not None
+    G._prefill(tm, st, emb, [(0, L0)])
+    st.next_ids.fill_(1000)
+    ps = st.persistent
+    h = ops.gather_rows(tm._w["embed"], st.next_ids, 1, 1, out=ps["h"])
+    ops.decode_layers(ps["wtab"], h, ps["workspace"], cos, sin, st.lens, st.K, st.V, ps["barrier"], ps["status"], cfg.hidden_size,
+                      cfg.intermediate_size, tm.Hq, tm.Hkv, cfg.rms_norm_eps, tm.D ** -0.5)
+    ops.decode_layers_status(ps["status"])
+    ws = ps["workspace"]
+    NQ, KO = (tm.Hq + 2 * tm.Hkv) * tm.D, tm.Hq * tm.D
+    w_qkv, w_attn = ws[:NQ].clone(), ws[NQ:NQ + KO].float().view(tm.Hq, tm.D)
+    Kc, Vc = st.K[0].clone(), st.V[0].clone()                       # [1, Hkv, Lmax, D], row L0 appended by the kernel
+    Q = ops.qwen_decode_qkprep(w_qkv.view(1, NQ), tm._w["l0.qn"], tm._w["l0.kn"], cos, sin, st.lens, Kc.clone(), Vc.clone(), 1, tm.Hq,
+                               tm.Hkv, tm.D, Lmax, cfg.rms_norm_eps).view(tm.Hq, tm.D)
+    Gq = tm.Hq // tm.Hkv
+    k = Kc[0, :, :L0 + 1].double().repeat_interleave(Gq, 0)
+    v = Vc[0, :, :L0 + 1].double().repeat_interleave(Gq, 0)
+    s = torch.einsum("hd,htd->ht", Q.double(), k) * tm.D ** -0.5
+    ref = torch.einsum("ht,htd->hd", torch.softmax(s, -1), v)
+    err = (w_attn.double() - ref).norm(dim=-1) / ref.norm(dim=-1)
+    assert torch.isfinite(w_attn).all() and (err <= 1e-2).all(), (int(err.argmax()), float(err.max()))
+
+
+def test_two_rows_long_prompts_on_the_per_projection_route():
+    """B = 2 (the per-projection route), prompts of 3000 and 700 tokens (the second left-padded): ragged cache lengths far past the
+    short tests', a long prefill after the padding is compacted away; each row matches its own full forward under the tie rule."""
+    from vggt_qwen3_amd import ops
+    tm, cfg = _qwen4b_dims(2)
+    torch.manual_seed(9)
+    L, NEW, n1 = 3000, 5, 700
+    emb = (torch.randn(2, L, cfg.hidden_size) * 0.5).to(BF16).cuda()
+    mask = torch.ones(2, L, dtype=torch.long).cuda()
+    mask[1, :L - n1] = 0
+    out, stats = tm.generate(inputs_embeds=emb, attention_mask=mask, max_new_tokens=NEW, use_graph=True, return_stats=True)
+    assert stats["persistent"] is False and out.shape == (2, NEW)
+    for b, lo in ((0, 0), (1, L - n1)):
+        logits = _full_forward_logits(tm, emb[b, lo:], out[b])
+        n = L - lo
+        for t in range(NEW):
+            row = logits[n - 1 + t]
+            assert row.max() - row[out[b, t]] < TIE_TOL, (b, t)
 
 
 def test_persistent_decode_reports_a_full_cache(ops):

@@ -487,7 +487,8 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_kernel(const bf16_t* _
         const bool ok = key_ok && qg < L && key <= qg;
         const float pv = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], sl2e, -lse4[i >> 2][i & 3])) : 0.f;
         p[i] = pv;
-        s[i] = pv * (dp[i] - del4[i >> 2][i & 3]) * scale;     // dS[q, key]
+        // selected, not just multiplied by pv = 0: a group that straddles L reads delta from the caller's slack, whatever it holds
+        s[i] = ok ? pv * (dp[i] - del4[i >> 2][i & 3]) * scale : 0.f;     // dS[q, key]
       }
 #pragma unroll
       for (int sp = 0; sp < 2; ++sp) {
