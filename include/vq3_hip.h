@@ -505,11 +505,16 @@ int vq3_qwen_flash_fwd(const void* Q, const void* K, const void* V, const void* 
 int vq3_qwen_flash_bwd(const void* Q, const void* K, const void* V, const void* keymask, const void* O, const void* dO,
                        const float* LSE, float* Delta, void* dQ, void* dK, void* dV, int32_t kv_parts, int32_t B, int32_t L,
                        int32_t Hq, int32_t Hkv, int32_t head_dim, int64_t ldo, int64_t lddo, float scale, void* stream);
-/* Benchmarking / test hook for vq3_gemm_bf16_nt's kernel choice on NT, K % 64 == 0 shapes: cfg = -3 restores the automatic
- * choice (the default), -1 the register-staged reference kernel, 0..14 a gemm2.hip tile configuration, 20 / 21 / 22 the
- * 8-phase kernels of gemm6.hip (256x256 / 256x128 / 128x256 tiles), 24 the two-workgroups-per-CU 256x128 kernel of gemm7.hip, 25 the
- * 256x256 kernel with the last round's tiles split along K, 30 whole rounds of 256x256 tiles + a row tail; 102 / 103 / 105 pin the schedule of the any-layout kernel
- * (gemm3.hip: 128x128 2-stage, 128x128 loader ring, 256x128 loader ring; -3 releases it too). Process-wide; not meant for concurrent use with launches on other threads. */
+/* Benchmarking / test hook for vq3_gemm_bf16_nt's kernel choice. cfg is -3 (restores the automatic choice, the default, on both paths
+ * below) or an id of the registry in csrc/gemm_config.h; any other value is an argument error that names it.
+ * NT, K % 64 == 0 shapes: 7 / 9 / 11 / 13 / 15 / 16 / 17 the tile configurations of gemm2.hip, 20 / 21 / 22 the 8-phase kernels of gemm6.hip
+ * (256x256 / 256x128 / 128x256 tiles), 24 the two-workgroups-per-CU 256x128 kernel of gemm7.hip, 25 the 256x256 kernel with the last
+ * round's tiles split along K, 30 whole rounds of 256x256 tiles + a row tail. Any other layout: 102 / 103 / 105 pin the schedule of
+ * gemm3.hip (128x128 2-stage, 128x128 loader ring, 256x128 loader ring), 106 / 107 the k-major form of the 256x256 kernel (without / with
+ * the last-round split). The environment variable VQ3_GEMM_CFG takes the same values; it is applied once, before the first GEMM call or
+ * the first call of this hook, whichever comes first (an id outside the registry fails every GEMM call), so a call of this hook always
+ * overrides it and holds whether it is made before or after the process's first GEMM.
+ * Process-wide; not meant for concurrent use with launches on other threads. */
 int vq3_gemm_force_config(int32_t cfg);
 
 /* Host-only test hook (no launch, no GPU needed): the workgroup -> tile map the GEMM kernels use for an M x N output cut into
@@ -521,7 +526,7 @@ int vq3_gemm_force_config(int32_t cfg);
 int vq3_gemm_tile_order(int32_t M, int32_t N, int32_t bm, int32_t bn, int32_t wg_per_cu, int32_t* xm_out, int32_t* band_out,
                         int32_t* order);
 
-/* Kernel-choice hygiene (gemm.hip: tuned_choice). The first call of a new (shape, layout, epilogue kind) times its candidate kernels
+/* Kernel-choice hygiene (gemm_tune.hip: tuned_choice). The first call of a new (shape, layout, epilogue kind) times its candidate kernels
  * unless a table entry answers. vq3_gemm_tune_table_load reads "M N K batch flags cfg" lines ('#' comments) into the table (the package
  * ships one for the Stage-1 shapes; VQ3_GEMM_TUNE_FILE=<path> still adds / appends). vq3_gemm_tune_workspace hands the tuner caller-owned
  * device memory for its trial output and cache-flush buffer (>= trial bytes + 320 MiB, 256-byte aligned; NULL, 0 detaches): with a

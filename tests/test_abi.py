@@ -51,6 +51,47 @@ def test_bad_args_fail_loudly_without_gpu():
     assert b"null" in lib.vq3_last_error()
 
 
+def test_gemm_force_config_rejects_an_id_outside_the_registry():
+    """vq3_gemm_force_config only takes ids of csrc/gemm_config.h (host state only: no launch, no GPU)."""
+    from vggt_qwen3_amd import _lib, ops
+    try:
+        for bad in (4, 14, 23, -1, -2, 104):                 # removed gemm2.hip cases, gaps of the id space, the old v1 kernel
+            with pytest.raises(_lib.Vq3Error, match=rf"(?<![\d-]){bad}(?!\d)"):
+                ops.gemm_force_config(bad)
+        for good in (7, 9, 11, 13, 15, 16, 17, 20, 21, 22, 24, 25, 30, 102, 103, 105, 106, 107):
+            ops.gemm_force_config(good)
+    finally:
+        ops.gemm_force_config(-3)                            # automatic choice again
+
+
+def test_gemm_cfg_environment_variable_rejects_an_id_outside_the_registry():
+    """VQ3_GEMM_CFG is applied at the first GEMM call, before the call's own arguments are looked at: a removed id fails that call and
+    names the id (no launch: the descriptor is empty); the hook overrides the variable, before or after that call."""
+    import os, subprocess, sys
+    code = (
+        "import ctypes, sys; sys.path.insert(0, sys.argv[1])\n"
+        "from vggt_qwen3_amd import _lib\n"
+        "lib = _lib.load(); d = _lib.GemmDesc()\n"
+        "if sys.argv[2] == 'hook_first': assert lib.vq3_gemm_force_config(102) == 0\n"
+        "rc = lib.vq3_gemm_bf16_nt(ctypes.byref(d), None); print(rc, lib.vq3_last_error().decode())\n"
+        "assert lib.vq3_gemm_force_config(-3) == 0\n"
+        "rc = lib.vq3_gemm_bf16_nt(ctypes.byref(d), None); print(rc, lib.vq3_last_error().decode())\n")
+
+    def run(value, order="gemm_first"):
+        env = dict(os.environ, VQ3_GEMM_CFG=value)
+        out = subprocess.run([sys.executable, "-c", code, str(ROOT), order], env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr
+        return out.stdout.strip().splitlines()
+
+    for order in ("gemm_first", "hook_first"):
+        first, second = run("4", order)
+        assert first.split()[0] != "0" and re.search(r"(?<![\d-])4(?!\d)", first) and "configuration" in first, first
+        assert second.split()[0] != "0" and "null" in second, second          # the hook's -3 replaced the bad value
+    for ok in ("13", "105", "-3"):
+        first, _ = run(ok)
+        assert "null" in first and "configuration" not in first, first
+
+
 def _tile_order(lib, M, N, bm, bn, wg):
     import numpy as np
     mt, nt = (M + bm - 1) // bm, (N + bn - 1) // bn

@@ -32,7 +32,7 @@ def load_window(path):
 
 def short(name: str) -> str:
     name = name.replace("(anonymous namespace)::", "").replace("vq3gemm::", "").replace("void ", "")
-    for fam in ("gemm_v2_kernel", "gemm_v3_kernel", "gemm_v6_kernel", "gemm_nt_kernel", "gemm_fp8_kernel", "flash_attn_hd64_kernel"):
+    for fam in ("gemm_v2_kernel", "gemm_v3_kernel", "gemm_v6_kernel", "gemm_fp8_kernel", "flash_attn_hd64_kernel"):
         if fam in name:
             return fam + "<" + name.split("<")[1].split(">")[0].replace(" ", "") + ">"
     if name.startswith("at::native::"):

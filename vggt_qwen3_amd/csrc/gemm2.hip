@@ -1,16 +1,13 @@
-// GEMM v2 for gfx950: LDS-DMA (global_load_lds_dwordx4) staged, 3-stage ring, counted vmcnt + raw s_barrier.
+// GEMM v2 for gfx950: LDS-DMA (global_load_lds_dwordx4) staged small-tile kernels, counted vmcnt + raw s_barrier.
 //
-// Same contract as gemm.hip's kernel (C = epilogue(alpha * A[M,K] . B[N,K]^T), NT, bf16 in / f32 MFMA accumulate), but
-// the operands never pass through VGPRs: every wave issues 1-KiB DMA pieces (8 tile rows x 128 B) straight into the
+// C = epilogue(alpha * A[M,K] . B[N,K]^T), NT, K % 64 == 0, bf16 in / f32 MFMA accumulate. The operands never pass through
+// VGPRs: the issuing waves send 1-KiB DMA pieces (8 tile rows x 128 B) straight into the
 // XOR-swizzled LDS image. The DMA destination is lane-linear (wave-uniform base + lane*16), so the swizzle
 // chunk' = chunk ^ (row & 7) is applied to each lane's SOURCE address (lane l reads k-chunk (l&7)^(l>>3) of row l>>3)
 // and again on the fragment reads - the same involution on both sides.
-// Pipeline, one barrier per 64-deep K step, tile t+1 always in flight across the barrier:
-//     s_waitcnt vmcnt(P)   (all but this wave's newest P pieces landed -> its share of tile t is in LDS)
-//     s_barrier            (everyone's share of tile t landed; everyone finished reading the stage tile t+2 reuses)
-//     issue tile t+2 -> stage (t+2)%3
-//     ds_read fragments of stage t%3, 16x16x32 bf16 MFMAs
-// One workgroup per CU (up to 144 KiB LDS), 8 waves for the 256x128 / 128x256 tiles, 4 for 128x128.
+// Two schedules, one barrier per 64-deep K step (the configurations are listed at launch_gemm_v2 and in gemm_config.h):
+//   NLOAD > 0: an NSTAGE-deep ring (3 or 4) filled by NLOAD dedicated loader waves, one workgroup per CU;
+//   NLOAD = 0: two stages, every wave issues its share of tile t+1 before it multiplies tile t, two workgroups per CU.
 #include "gemm_common.h"
 
 namespace vq3gemm {
@@ -28,6 +25,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
   constexpr int NISS = NLOAD > 0 ? NLOAD : NW;            // waves that issue DMA
   constexpr int PPW = NPIECE / NISS;                     // pieces per issuing wave per stage
   static_assert(NPIECE % NISS == 0, "pieces must divide evenly over the issuing waves");
+  static_assert(NLOAD > 0 ? (NSTAGE == 3 || NSTAGE == 4) : NSTAGE == 2, "a loader ring of 3 or 4 stages, or two stages without loader waves");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
       }
     }
   };
-  if (NSTAGE >= 3 && NLOAD > 0) {
+  if (NLOAD > 0) {
     // producer / consumer split inside the workgroup (one s_barrier per K step for everybody):
     //   loader waves:  wait until their pieces of tile t landed -> barrier -> issue tile t+2
     //   compute waves: barrier -> fragments of tile t -> MFMAs
@@ -147,8 +145,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
       int stage = 0;
       for (int t = 0; t < nt; ++t) {
         const int newer = (last - t) < (NSTAGE - 2) ? (last - t) : (NSTAGE - 2);   // tiles allowed to stay in flight
-        if (newer >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PPW) : "memory");
-        else if (newer == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
+        if (newer == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
         else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -167,26 +164,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
       compute(stage);
       stage = stage == NSTAGE - 1 ? 0 : stage + 1;
     }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    prefetch_epilogue();
-    compute(stage);
-  } else if (NSTAGE == 3) {
-    issue(0, 0);
-    if (nt > 1) issue(1, 1);
-    int stage = 0;
-    for (int t = 0; t < last; ++t) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      if (t + 2 <= last) {
-        int s2 = stage + 2; s2 = s2 >= 3 ? s2 - 3 : s2;
-        issue(t + 2, s2);
-      }
-      compute(stage);
-      stage = stage == 2 ? 0 : stage + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     prefetch_epilogue();
@@ -300,19 +277,9 @@ int launch_cfg(GemmParams& p, int nbatch, hipStream_t stream) {
 
 int launch_gemm_v2(GemmParams& p, int cfg, int nbatch, hipStream_t stream) {
   switch (cfg) {
-    case 0: return launch_cfg<256, 128, 4, 2, 3>(p, nbatch, stream);
-    case 1: return launch_cfg<128, 256, 2, 4, 3>(p, nbatch, stream);
-    case 2: return launch_cfg<128, 128, 2, 2, 3>(p, nbatch, stream);
-    case 3: return launch_cfg<128, 128, 4, 2, 3>(p, nbatch, stream);
-    case 4: return launch_cfg<128, 64, 4, 2, 3>(p, nbatch, stream);
-    case 5: return launch_cfg<64, 128, 2, 4, 3>(p, nbatch, stream);
-    case 6: return launch_cfg<128, 128, 2, 2, 2>(p, nbatch, stream);
     case 7: return launch_cfg<128, 128, 4, 2, 2>(p, nbatch, stream);
-    case 8: return launch_cfg<256, 128, 4, 2, 3, 4>(p, nbatch, stream);
     case 9: return launch_cfg<128, 128, 4, 2, 3, 4>(p, nbatch, stream);
-    case 10: return launch_cfg<128, 128, 2, 2, 3, 4>(p, nbatch, stream);
     case 11: return launch_cfg<256, 128, 4, 2, 3, 2>(p, nbatch, stream);
-    case 12: return launch_cfg<128, 128, 4, 2, 3, 2>(p, nbatch, stream);
     case 13: return launch_cfg<128, 128, 4, 2, 4, 2>(p, nbatch, stream);
     // 224 x 128 / 192 x 128 (7 x 2 / 6 x 2 MFMA tiles per wave): M = 6174 = 27.6 x 224 gives 224 tiles for N = 1024 (0.875 fill in
     // one round instead of 0.78) - measured: ties 256 x 128 (the 7 x 2 wave tile moves 0.64 KB of LDS per MFMA, and a single
@@ -323,7 +290,7 @@ int launch_gemm_v2(GemmParams& p, int cfg, int nbatch, hipStream_t stream) {
     // At K = 1024 a tile's epilogue (staging C through LDS + the row stores: 8-9 us of a 24 us tile on the 8-wave kernels, during which
     // the MFMA pipe idles - tools/gemm_stamps.py) runs under the co-resident workgroup's main loop; M = 49 392 = 257.25 x 192.
     case 17: return launch_cfg<192, 128, 2, 2, 2>(p, nbatch, stream);
-    default: return launch_cfg<128, 128, 4, 2, 5, 2>(p, nbatch, stream);
+    default: return -1;      // not a configuration of this file (gemm_config.h lists them): nothing launched
   }
 }
 

@@ -803,7 +803,7 @@ inline void choose_tile_order(GemmParams& p, int BM, int BN, int wg_per_cu) {
   p.xm = bxm; p.nbw = bnb;
 }
 
-// v2 (LDS-DMA pipelined) launcher, defined in gemm2.hip. cfg: 0 = 256x128 tile, 1 = 128x256, 2 = 128x128.
+// v2 (LDS-DMA pipelined) launcher, defined in gemm2.hip. cfg: one of gemm_config.h's CFG_V2_* ids; -1 (nothing launched) for any other.
 int launch_gemm_v2(GemmParams& p, int cfg, int nbatch, hipStream_t stream);
 // v6 (256x256 tile, 8-phase schedule, NT, K % 64 == 0), defined in gemm6.hip.
 int launch_gemm_v6(GemmParams& p, int shape, int nbatch, hipStream_t stream);   // shape: 0 = 256x256, 1 = 256x128, 2 = 128x256,
@@ -821,7 +821,7 @@ void gemm_split_set_provider(vq3_ws_provider_t fn);
 // v7 (256x128 tile, four waves, two workgroups per CU: a tile's epilogue runs under the co-resident workgroup's main loop), gemm7.hip.
 // Returns -1 (nothing launched) when the problem is outside its contract: the caller picks another kernel.
 int launch_gemm_v7(GemmParams& p, int nbatch, hipStream_t stream);
-// v3 (any operand layout, K % 8 == 0), defined in gemm3.hip. nstage: 2 or 3.
+// v3 (any operand layout, K % 8 == 0), defined in gemm3.hip. nstage: 2, 3 or 5 (256x128 tile).
 int launch_gemm_v3(GemmParams& p, int transA, int transB, int nstage, int nbatch, hipStream_t stream);
 
 }  // namespace vq3gemm

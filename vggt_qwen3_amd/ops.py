@@ -1020,7 +1020,8 @@ def gemm_split_debug_spin_bound(polls: int = 0) -> None:
 
 
 def gemm_force_config(cfg: int = -3) -> None:
-    """Force vq3_gemm_bf16_nt's tile configuration for NT shapes (-3 = automatic). Benchmarks and tests only."""
+    """Force vq3_gemm_bf16_nt's kernel configuration: an id of csrc/gemm_config.h (7 / 9 / 11 / 13 / 15 / 16 / 17, 20 / 21 / 22, 24, 25, 30 for
+    NT shapes; 102 / 103 / 105 / 106 / 107 for the other layouts), -3 = automatic. Any other id raises. Benchmarks and tests only."""
     check(_lib.load().vq3_gemm_force_config(cfg), "vq3_gemm_force_config")
 
 
