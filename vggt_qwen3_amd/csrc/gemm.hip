@@ -295,10 +295,7 @@ static int gemm_dispatch(const vq3_gemm_desc* d, const vq3_vit_qkv_epilogue* ve,
     if (int rc = attach_swiglu_bwd(p, d, sw_gu, sw_dgu)) return rc;
   if (sw_fwd_gu)
     if (int rc = attach_swiglu_fwd(p, d, sw_fwd_gu, ve || sw_dgu || ln)) return rc;
-  const int esz = d->out_f32 ? 4 : 2;
-  bool vec = (p.ldc % 4 == 0) && (p.sC1 % 4 == 0) && (p.sC2 % 4 == 0) && ((uintptr_t)p.C % (4 * esz) == 0);
-  if (d->R) vec = vec && (d->ldr % 4 == 0) && (d->sR1 % 4 == 0) && (d->sR2 % 4 == 0) && ((uintptr_t)d->R % (4 * esz) == 0);
-  p.vec_ok = vec ? 1 : 0;
+  p.vec_ok = host_vec_ok(p) ? 1 : 0;
 
   hipStream_t s = (hipStream_t)stream;
   const int nbatch = d->nb1 * d->nb2;

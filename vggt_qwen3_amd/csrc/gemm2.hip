@@ -34,16 +34,9 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
   const int wm = (wid % NW) / WN, wn = wid % WN;
   int m0, n0;
   tile_coords(p, BM, BN, m0, n0);
-  // folded LayerNorm: thread r < BM fetches row r's statistics now (two registers through the main loop) - at the epilogue the
-  // round trip to L2 / HBM would be exposed on every tile
-  static_assert(BM <= 64 * WM * WN, "one statistics thread per tile row");
   float ln_mu = 0.f, ln_rs = 0.f;
-  if (p.ln_in && tid < BM) ln_row(p, m0 + tid, ln_mu, ln_rs);
-  const int b1 = blockIdx.z / p.nb2, b2 = blockIdx.z % p.nb2;
-  const bf16_t* A = p.A + b1 * p.sA1 + b2 * p.sA2;
-  const bf16_t* B = p.B + b1 * p.sB1 + (long)(b2 / p.b2divB) * p.sB2;
-  const long coff = b1 * p.sC1 + b2 * p.sC2;
-  const long roff = b1 * p.sR1 + b2 * p.sR2;
+  ln_row_early<BM, 64 * NW>(p, m0, tid, ln_mu, ln_rs);
+  VQ3_BATCH_OPERANDS(p, A, B, coff, roff);
 
   // ---- DMA source pointers: piece pi = wid + NW*j covers tile rows 8*pi .. 8*pi+7 of [A rows | B rows]
   const int prow = lane >> 3;                       // row inside the piece (== row & 7 of the tile row)
@@ -120,7 +113,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       int n = n0 + wn * (BN / WN) + j * 16 + 4 * fq;
-      n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);     // clamped lanes fall back to the generic path at store time
+      n = quad_col(p, n);
       if (p.bias) bias_r[j] = *reinterpret_cast<const f32x4*>(p.bias + n);
       if (p.colscale) cs_r[j] = *reinterpret_cast<const f32x4*>(p.colscale + n);
       if (PRE_RES && p.R) {
@@ -138,23 +131,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
     //   loader waves:  wait until their pieces of tile t landed -> barrier -> issue tile t+2
     //   compute waves: barrier -> fragments of tile t -> MFMAs
     if (loader) {
-      // the ring runs NSTAGE-1 tiles ahead: cold (HBM-resident) weights need more than two tiles of latency cover
-#pragma unroll
-      for (int i = 0; i < NSTAGE - 1; ++i)
-        if (i < nt) issue(i, i);
-      int stage = 0;
-      for (int t = 0; t < nt; ++t) {
-        const int newer = (last - t) < (NSTAGE - 2) ? (last - t) : (NSTAGE - 2);   // tiles allowed to stay in flight
-        if (newer == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
-        else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t + NSTAGE - 1 <= last) {
-          int s2 = stage + NSTAGE - 1; s2 = s2 >= NSTAGE ? s2 - NSTAGE : s2;
-          issue(t + NSTAGE - 1, s2);
-        }
-        stage = stage == NSTAGE - 1 ? 0 : stage + 1;
-      }
+      VQ3_LOADER_RING(NSTAGE, PPW, nt, issue);
       return;
     }
     int stage = 0;
@@ -187,84 +164,26 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (NSTAGE == 2 ? 2 : 1) * ((W
   }
 
   if (!OUT_F32 && staged) {
-    // loader waves have returned; the compute waves meet once (all fragment reads of the last stage are done), lay the
-    // finished tile out in LDS and store whole rows
-    f32x4 bias_v[TN], cs_v[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      int n = n0 + wn * (BN / WN) + j * 16 + 4 * fq;
-      n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);
-      if (p.bias) bias_v[j] = *reinterpret_cast<const f32x4*>(p.bias + n);
-      if (p.colscale) cs_v[j] = *reinterpret_cast<const f32x4*>(p.colscale + n);
-    }
-    __syncthreads();
-    if (p.ln_in) {      // folded LayerNorm: rstd (acc - mu c) per lane-owned row, before the usual epilogue
-      f32x4 cc[TN];
-      float mu[TM], rs[TM];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) cc[j] = ln_colsum(p, n0 + wn * (BN / WN) + j * 16 + 4 * fq);
-      if (tid < BM) reinterpret_cast<float2*>(smem)[tid] = float2{ln_mu, ln_rs};   // (barrier above: the last stage's reads are done)
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const float2 v = reinterpret_cast<const float2*>(smem)[wm * (BM / WM) + i * 16 + fr];
-        mu[i] = v.x; rs[i] = v.y;
-      }
-      __syncthreads();                                       // before the C image overwrites the pairs
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = ln_apply(acc[i][j], mu[i], rs[i], cc[j]);
-    }
-#define V2_STAGE(ACT_, MODE_)                                                                                                       \
-  do {                                                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                                  \
-      _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                                                \
-        stage_quad<BN, ACT_, MODE_>(p, smem, wm * (BM / WM) + i * 16 + fr, wn * (BN / WN) + j * 16 + 4 * fq, acc[i][j], bias_v[j], cs_v[j]); \
-  } while (0)
-    VQ3_STAGE_DISPATCH(p, V2_STAGE);
-#undef V2_STAGE
-    __syncthreads();
-    staged_store<BM, BN>(p, smem, coff, roff, m0, n0, tid, 64 * NW);
+    VQ3_STAGED_EPILOGUE_RM();
     return;
   }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * (BM / WM) + i * 16 + fr;
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * 16 + 4 * fq;
-      if (n >= p.N) continue;
-      if (pre_ok && n + 3 < p.N) {
-        u32x2 rv = res_r[PRE_RES ? i : 0][j];
-        if (!PRE_RES && p.R)
-          rv = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(p.R) + roff + (long)m * p.ldr + n);
-        store_quad_pre(p, coff, m, n, acc[i][j], bias_r[j], cs_r[j], rv);
-      }
-      else store_quad<OUT_F32>(p, coff, roff, m, n, acc[i][j]);
+  VQ3_DIRECT_STORE(TM, TN, m0 + wm * (BM / WM) + i * 16 + fr, n0 + wn * (BN / WN) + j * 16 + 4 * fq, {
+    if (pre_ok && n + 3 < p.N) {
+      u32x2 rv = res_r[PRE_RES ? i : 0][j];
+      if (!PRE_RES && p.R)
+        rv = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(p.R) + roff + (long)m * p.ldr + n);
+      store_quad_pre(p, coff, m, n, acc[i][j], bias_r[j], cs_r[j], rv);
     }
-  }
+    else store_quad<OUT_F32>(p, coff, roff, m, n, acc[i][j]);
+  });
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE, int NLOAD = 0>
 int launch_cfg(GemmParams& p, int nbatch, hipStream_t stream) {
   constexpr int SMEM = NSTAGE * (BM + BN) * 128;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)gemm_v2_kernel<BM, BN, WM, WN, NSTAGE, NLOAD, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    hipError_t e2 = hipFuncSetAttribute((const void*)gemm_v2_kernel<BM, BN, WM, WN, NSTAGE, NLOAD, false>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      vq3_set_error("gemm v2: hipFuncSetAttribute failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-      return 2;
-    }
-    attr_done = true;
-  }
-  p.mtiles = (p.M + BM - 1) / BM;
-  p.ntiles = (p.N + BN - 1) / BN;
-  choose_tile_order(p, BM, BN, NSTAGE == 2 ? 2 : 1);
+  if (int rc = prepare_launch<gemm_v2_kernel<BM, BN, WM, WN, NSTAGE, NLOAD, true>, gemm_v2_kernel<BM, BN, WM, WN, NSTAGE, NLOAD, false>>(
+          p, "gemm v2", SMEM, BM, BN, NSTAGE == 2 ? 2 : 1))
+    return rc;
   dim3 grid(p.mtiles * p.ntiles, 1, nbatch);
   if (p.out_f32)
     hipLaunchKernelGGL((gemm_v2_kernel<BM, BN, WM, WN, NSTAGE, NLOAD, true>), grid, dim3(64 * (WM * WN + NLOAD)), SMEM, stream, p);

@@ -93,11 +93,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v6_kernel(GemmParams p) {
   // through the main loop; the 256 x 256 kernel has none to spare (spills, 3 % on every launch) and fetches them inside the epilogue
   constexpr bool LN_EARLY = (AH + BH) < 4;
   float ln_mu = 0.f, ln_rs = 0.f;
-  const int b1 = blockIdx.z / p.nb2, b2 = blockIdx.z % p.nb2;
-  const bf16_t* A = p.A + b1 * p.sA1 + b2 * p.sA2;
-  const bf16_t* B = p.B + b1 * p.sB1 + (long)(b2 / p.b2divB) * p.sB2;
-  const long coff = b1 * p.sC1 + b2 * p.sC2;
-  const long roff = b1 * p.sR1 + b2 * p.sR2;
+  VQ3_BATCH_OPERANDS(p, A, B, coff, roff);
 
   // ---- DMA sources. A half-tile is 16 pieces of 8 rows x 128 B; wave w issues pieces w and w + 8. Lane l of a piece
   // reads k-chunk (l & 7) ^ (l >> 3) of row l >> 3 (the read-side swizzle chunk ^ (row & 7), applied to the source).
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v6_kernel(GemmParams p) {
   if (p.stamps && tid == 0)
     p.stamps[(long)tile * 8 + 7] = ((unsigned long long)blockIdx.x << 32) | __builtin_amdgcn_s_getreg(6164 /* HW_REG_XCC_ID, 4 bits */) |
                                    ((unsigned long long)(__builtin_amdgcn_s_getreg(63492 /* HW_REG_HW_ID, 32 bits */) & 0xff00u) << 8);   // CU / SH / SE id -> bits 16-23
-  if (HAS_LN && LN_EARLY && p.ln_in && tid < BM) ln_row(p, m0 + tid, ln_mu, ln_rs);
+  if constexpr (HAS_LN && LN_EARLY) ln_row_early<BM, 512>(p, m0, tid, ln_mu, ln_rs);
 #pragma unroll
   for (int i = 0; i < AH * 4; ++i)
 #pragma unroll
@@ -563,12 +559,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v6_kernel(GemmParams p) {
 #pragma unroll
     for (int j = 0; j < BH; ++j)
 #pragma unroll
-      for (int nt2 = 0; nt2 < 2; ++nt2) {
-        int n = n0 + j * 128 + wc * 32 + nt2 * 16 + 4 * fq;
-        n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);          // columns past N are never stored
-        if (p.bias) bias_r[j][nt2] = *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (p.colscale) cs_r[j][nt2] = *reinterpret_cast<const f32x4*>(p.colscale + n);
-      }
+      for (int nt2 = 0; nt2 < 2; ++nt2) load_col_vectors(p, n0 + j * 128 + wc * 32 + nt2 * 16 + 4 * fq, bias_r[j][nt2], cs_r[j][nt2]);
     EpiPre pre;
     pre.on = false;
     if constexpr (EK == 0) staged_prefetch<BM, BN>(p, coff, roff, m0, n0, tid, 512, pre);
@@ -598,8 +589,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v6_kernel(GemmParams p) {
         const int li = (q >> 1) * 128 + wc * 32 + (q & 1) * 16 + 4 * fq;
         int n = n0 + li;
         if constexpr (EK == 4) n = li < BN / 2 ? (n0 >> 1) + li : (p.N >> 1) + (n0 >> 1) + li - BN / 2;       // (the weight row a tile column multiplies)
-        n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);
-        f8c[q] = p.f8_cs ? *reinterpret_cast<const f32x4*>(p.f8_cs + n) : f32x4{1.f, 1.f, 1.f, 1.f};
+        f8c[q] = p.f8_cs ? *reinterpret_cast<const f32x4*>(p.f8_cs + quad_col(p, n)) : f32x4{1.f, 1.f, 1.f, 1.f};
       }
     }
     // fused q|k|v store: the rows' output offsets and RoPE table rows, one thread per row, in 4 KiB above the LayerNorm pairs (never
@@ -644,22 +634,7 @@ __global__ __launch_bounds__(512, 2) void gemm_v6_kernel(GemmParams p) {
           if (LN_FUSED) __builtin_amdgcn_sched_barrier(0);      // one 16-row group at a time (register pressure)
         }
     };
-    // activation, bias / LayerScale / alpha and the LayerNorm fold are dispatched ONCE per tile (gemm_common.h: VQ3_STAGE_DISPATCH); the
-    // fused q|k|v and SwiGLU epilogues never carry an activation or LayerScale
-#define V6_STAGE(ACT_, MODE_)                                                                                                     \
-  do {                                                                                                                            \
-    if constexpr (EK == 3) stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{}); \
-    else if constexpr (EK == 1) {                                                                                                 \
-      if (ln_on) stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{});          \
-      else stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});               \
-    } else stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});               \
-  } while (0)
-    if constexpr (EK == 2 || EK == 4) V6_STAGE(0, 0);            // (host: no bias, no LayerScale, alpha == 1)
-    else if constexpr (EK == 1) {
-      if (p.bias && p.alpha == 1.f) V6_STAGE(0, 1);
-      else V6_STAGE(0, -1);
-    } else VQ3_STAGE_DISPATCH(p, V6_STAGE);
-#undef V6_STAGE
+    VQ3_STAGE_DISPATCH_EK(p, EK, ln_on, stage_all);
     V6_STAMP(6);    // this wave's quads are in the C image
     if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next tile's K tiles 0 and 1 has landed
     __syncthreads();
@@ -779,47 +754,36 @@ int sk_plan(const GemmParams& p, int nbatch, int ncu, int* full, int* rem, int k
   return sl;
 }
 
+// CUs of the device, rounded down to a multiple of 8: persistent workgroups stride over the tile order by it and stay on their XCD's slice
+int cu_count8() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    (void)hipGetLastError();
+    ncu = n / 8 * 8;
+  }
+  return ncu;
+}
+
 template <int AH, int BH>
 int launch_v6(GemmParams& p, int nbatch, hipStream_t stream, bool split = false) {
   // (two-phase variants: two K-tile buffers of the NEXT tile + the C image of the current one, or three K-tile buffers: 160 KiB)
   constexpr int SMEM = (AH + BH == 4) ? 2 * 4 * HALF + 2048 + 4096 + 8192 : 2 * 3 * HALF + 128 * AH * 128 * BH * 2;   // (+ 2 KiB: LayerNorm pairs above the C image, + 4 KiB: the fused q|k|v store's row table, + 8 KiB: its cos / sin tables)
   static_assert(SMEM <= 160 * 1024 && (AH + BH == 4 || SMEM >= 3 * (AH + BH) * HALF), "LDS budget");
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    hipError_t e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<AH, BH, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if constexpr (AH + BH == 4)
-      if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if constexpr (AH + BH == 4)
-      if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if constexpr (AH + BH == 4)
-      if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      vq3_set_error("gemm v6: hipFuncSetAttribute failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-      return 2;
-    }
-    attr_done = true;
-  }
   // bf16 output that cannot take the LDS-staged epilogue (rows not 16-byte aligned): the loader-ring kernel keeps the per-quad path
   if (p.epi == 3 && (p.out_f32 || !host_staged_ok(p) || (p.N >> 1) % (64 * BH) != 0)) {
     vq3_set_error("gemm v6: the SwiGLU-forward epilogue needs the staged bf16 path and I %% %d == 0", 64 * BH);
     return 1;
   }
   if (!p.out_f32 && !host_staged_ok(p)) return launch_gemm_v2(p, AH == 2 ? 11 : 13, nbatch, stream);
-  p.mtiles = (p.M + 128 * AH - 1) / (128 * AH);
-  p.ntiles = (p.N + 128 * BH - 1) / (128 * BH);
-  choose_tile_order(p, 128 * AH, 128 * BH, 1);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    (void)hipGetLastError();
-    ncu = n / 8 * 8;                 // persistent workgroups stride over the tile order by a multiple of 8: they stay on their XCD's slice
-  }
+  if (int rc = prepare_launch<gemm_v6_kernel<AH, BH, true, 0>, gemm_v6_kernel<AH, BH, false, 0>, gemm_v6_kernel<AH, BH, false, 1>, gemm_v6_kernel<AH, BH, false, 2>,
+                              gemm_v6_kernel<AH, BH, false, 3>, gemm_v6_kernel<AH, BH, false, 4>>(p, "gemm v6", SMEM, 128 * AH, 128 * BH, 1))
+    return rc;
+  if constexpr (AH + BH == 4)
+    if (int rc = set_dynamic_lds<gemm_v6_kernel<2, 2, false, 0, true>, gemm_v6_kernel<2, 2, false, 1, true>, gemm_v6_kernel<2, 2, false, 3, true>>("gemm v6", SMEM))
+      return rc;
+  const int ncu = cu_count8();
   if (const char* sp = getenv("VQ3_GEMM_STAMP_PTR")) p.stamps = (unsigned long long*)strtoull(sp, nullptr, 0);   // diagnostics only
   static int stagger_env = -1;
   if (stagger_env < 0) { const char* e = getenv("VQ3_V6_STAGGER"); stagger_env = e ? atoi(e) : 0; }
@@ -863,31 +827,13 @@ int launch_v6(GemmParams& p, int nbatch, hipStream_t stream, bool split = false)
 // that applies. Returns -1 (nothing launched) outside the contract: the caller takes the loader-ring kernel of gemm_fp8.hip.
 int launch_gemm_v6_f8(GemmParams& p, hipStream_t stream) {
   constexpr int SMEM = 2 * 4 * HALF + 2048;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) {
-      vq3_set_error("gemm v6 (e4m3): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
   if (p.out_f32 || !host_staged_ok(p) || p.K % 128 != 0 || p.ln_in || p.st_out) return -1;
   if (p.epi == 3 && (p.N >> 1) % 128 != 0) return -1;
   if (p.epi == 1) return -1;
-  p.mtiles = (p.M + 255) / 256;
-  p.ntiles = (p.N + 255) / 256;
-  choose_tile_order(p, 256, 256, 1);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    (void)hipGetLastError();
-    ncu = n / 8 * 8;
-  }
+  if (int rc = prepare_launch<gemm_v6_kernel<2, 2, false, 0, false, true>, gemm_v6_kernel<2, 2, false, 0, true, true>, gemm_v6_kernel<2, 2, false, 2, false, true>,
+                              gemm_v6_kernel<2, 2, false, 4, false, true>>(p, "gemm v6 (e4m3)", SMEM, 256, 256, 1))
+    return rc;
+  const int ncu = cu_count8();
   p.stagger = 0;
   const dim3 grid(p.mtiles * p.ntiles, 1, 1);
   if (p.epi == 2) hipLaunchKernelGGL((gemm_v6_kernel<2, 2, false, 2, false, true>), grid, dim3(512), SMEM, stream, p);
@@ -909,34 +855,16 @@ int launch_gemm_v6_f8(GemmParams& p, hipStream_t stream) {
 // its contract (nothing launched): the caller keeps gemm3.hip's kernels.
 int launch_gemm_v6_km(GemmParams& p, int nbatch, hipStream_t stream, bool split) {
   constexpr int SMEM = 2 * 4 * HALF + 2048;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v6_kernel<2, 2, false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) {
-      vq3_set_error("gemm v6 (k-major): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
   if (nbatch != 1 || p.out_f32 || p.epi != 0 || p.ln_in || p.nsplit != 1 || !host_staged_ok(p) || p.M % 8 || p.N % 8 || p.K % 8 || p.M < 8 || p.N < 8)
     return -1;
   // (byte offsets of a tile's k rows are 32-bit: 63 rows of either operand must stay below 4 GiB)
   if ((long)64 * p.lda * 2 + (long)p.M * 2 >= (1l << 32) || (long)64 * p.ldb * 2 + (long)p.N * 2 >= (1l << 32)) return -1;
-  p.mtiles = (p.M + 255) / 256;
-  p.ntiles = (p.N + 255) / 256;
-  choose_tile_order(p, 256, 256, 1);
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    (void)hipGetLastError();
-    ncu = n / 8 * 8;
-  }
   p.stagger = 0;
   // (the last-round K split is not offered here: with the k-major fragment addresses on top of the split's state the 256-register kernel
   // spills 133 registers, 26 scratch instructions per main-loop trip - built and measured once: the down-projection weight gradient,
   // 380 tiles = 256 + 124 x 2 halves, 1871 us against 571 unsplit)
   if (split) return -1;
+  if (int rc = prepare_launch<gemm_v6_kernel<2, 2, false, 0, false, false, true>>(p, "gemm v6 (k-major)", SMEM, 256, 256, 1)) return rc;
   hipLaunchKernelGGL((gemm_v6_kernel<2, 2, false, 0, false, false, true>), dim3(p.mtiles * p.ntiles, 1, 1), dim3(512), SMEM, stream, p);
   return 0;
 }

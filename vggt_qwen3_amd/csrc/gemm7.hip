@@ -49,11 +49,7 @@ __global__ __launch_bounds__(256, 2) void gemm_v7_kernel(GemmParams p) {
   // folded LayerNorm: thread r fetches row r's statistics now (two registers through the main loop; the round trip runs under the prologue)
   float ln_mu = 0.f, ln_rs = 0.f;
   if (HAS_LN && p.ln_in) ln_row(p, m0 + tid, ln_mu, ln_rs);
-  const int b1 = blockIdx.z / p.nb2, b2 = blockIdx.z % p.nb2;
-  const bf16_t* A = p.A + b1 * p.sA1 + b2 * p.sA2;
-  const bf16_t* B = p.B + b1 * p.sB1 + (long)(b2 / p.b2divB) * p.sB2;
-  const long coff = b1 * p.sC1 + b2 * p.sC2;
-  const long roff = b1 * p.sR1 + b2 * p.sR2;
+  VQ3_BATCH_OPERANDS(p, A, B, coff, roff);
 
   // ---- DMA sources. A half-tile is 16 pieces of 8 rows x 128 B; wave w issues pieces w, w + 4, w + 8, w + 12. Lane l of a piece reads
   // k-chunk (l & 7) ^ (l >> 3) of row l >> 3 (the read-side swizzle chunk ^ (row & 7), applied to the source).
@@ -155,10 +151,7 @@ __global__ __launch_bounds__(256, 2) void gemm_v7_kernel(GemmParams p) {
   f32x4 bias_r[4], cs_r[4];
 #pragma unroll
   for (int nt2 = 0; nt2 < 4; ++nt2) {
-    int n = n0 + wc * 64 + nt2 * 16 + 4 * fq;
-    n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);                 // columns past N are never stored
-    if (p.bias) bias_r[nt2] = *reinterpret_cast<const f32x4*>(p.bias + n);
-    if (p.colscale) cs_r[nt2] = *reinterpret_cast<const f32x4*>(p.colscale + n);
+    const int n = load_col_vectors(p, n0 + wc * 64 + nt2 * 16 + 4 * fq, bias_r[nt2], cs_r[nt2]);
     if (ln_on) cc[nt2] = ln_colsum(p, n);
   }
   EpiPre pre;
@@ -193,20 +186,7 @@ __global__ __launch_bounds__(256, 2) void gemm_v7_kernel(GemmParams p) {
         }
       }
   };
-#define V7_STAGE(ACT_, MODE_)                                                                                                     \
-  do {                                                                                                                            \
-    if constexpr (EK == 3) stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{}); \
-    else if constexpr (EK == 1) {                                                                                                 \
-      if (ln_on) stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{});          \
-      else stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});               \
-    } else stage_all(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});               \
-  } while (0)
-  if constexpr (EK == 2 || EK == 4) V7_STAGE(0, 0);              // (host: no bias, no LayerScale, alpha == 1)
-  else if constexpr (EK == 1) {
-    if (p.bias && p.alpha == 1.f) V7_STAGE(0, 1);
-    else V7_STAGE(0, -1);
-  } else VQ3_STAGE_DISPATCH(p, V7_STAGE);
-#undef V7_STAGE
+  VQ3_STAGE_DISPATCH_EK(p, EK, ln_on, stage_all);
   __syncthreads();
   staged_store<BM, BN, (EK == 3 ? 0 : EK)>(p, smem, coff, roff, m0, n0, tid, 256, &pre);
 }
@@ -214,18 +194,8 @@ __global__ __launch_bounds__(256, 2) void gemm_v7_kernel(GemmParams p) {
 constexpr int SMEM7 = NSLOT7 * HALF7;      // 80 KiB: two workgroups per CU
 
 template <int EK>
-int launch_ek(const GemmParams& p, dim3 grid, hipStream_t stream) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)gemm_v7_kernel<EK>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM7);
-    if (e != hipSuccess) {
-      vq3_set_error("gemm v7: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+void launch_ek(const GemmParams& p, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL((gemm_v7_kernel<EK>), grid, dim3(256), SMEM7, stream, p);
-  return 0;
 }
 
 }  // namespace
@@ -237,15 +207,15 @@ int launch_gemm_v7(GemmParams& p, int nbatch, hipStream_t stream) {
   if (p.out_f32 || !host_staged_ok(p) || p.K % BK7 != 0) return -1;
   if (p.epi == 3 && (p.N >> 1) % 64 != 0) return -1;
   if ((p.epi == 2 || p.epi == 3) && p.ln_in) return -1;
-  p.mtiles = (p.M + 255) / 256;
-  p.ntiles = (p.N + 127) / 128;
-  choose_tile_order(p, 256, 128, 2);
+  if (int rc = prepare_launch<gemm_v7_kernel<0>, gemm_v7_kernel<1>, gemm_v7_kernel<2>, gemm_v7_kernel<3>, gemm_v7_kernel<4>>(p, "gemm v7", SMEM7, 256, 128, 2))
+    return rc;
   const dim3 grid(p.mtiles * p.ntiles, 1, nbatch);
-  if (p.epi == 1) return launch_ek<1>(p, grid, stream);
-  if (p.epi == 2) return launch_ek<2>(p, grid, stream);
-  if (p.epi == 3) return launch_ek<4>(p, grid, stream);
-  if (p.ln_in) return launch_ek<3>(p, grid, stream);
-  return launch_ek<0>(p, grid, stream);
+  if (p.epi == 1) launch_ek<1>(p, grid, stream);
+  else if (p.epi == 2) launch_ek<2>(p, grid, stream);
+  else if (p.epi == 3) launch_ek<4>(p, grid, stream);
+  else if (p.ln_in) launch_ek<3>(p, grid, stream);
+  else launch_ek<0>(p, grid, stream);
+  return 0;
 }
 
 }  // namespace vq3gemm

@@ -96,10 +96,30 @@ __device__ __forceinline__ void ln_row(const GemmParams& p, int m, float& mu, fl
 // The kernels fetch the statistics one thread per tile row at their start (two registers through the main loop), pass the (mu, rstd)
 // pairs through LDS at the epilogue and every lane reads its own rows' pair from there. Loaded per lane instead, the 16 lanes that
 // share a row would each request its 64 bytes - 256 KB of load traffic per 256-row tile through the texture path (+3.7 us per tile).
-__device__ __forceinline__ f32x4 ln_colsum(const GemmParams& p, int n) {
-  n = n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0);     // columns past N are never stored
-  return *reinterpret_cast<const f32x4*>(p.ln_c + n);
+template <int BM, int NTHREADS>
+__device__ __forceinline__ void ln_row_early(const GemmParams& p, int m0, int tid, float& mu, float& rs) {
+  static_assert(BM <= NTHREADS, "one statistics thread per tile row");
+  if (p.ln_in && tid < BM) ln_row(p, m0 + tid, mu, rs);
 }
+// first column of the 16-byte column-vector load (bias, LayerScale, LayerNorm column sums, e4m3 scales) behind a lane's quad n .. n + 3:
+// clamped into [0, N), because columns past N are never stored (a clamped lane takes the element-wise path at store time)
+__device__ __forceinline__ int quad_col(const GemmParams& p, int n) { return n + 3 < p.N ? n : (p.N >= 4 ? p.N - 4 : 0); }
+__device__ __forceinline__ f32x4 ln_colsum(const GemmParams& p, int n) { return *reinterpret_cast<const f32x4*>(p.ln_c + quad_col(p, n)); }
+// a lane's bias / LayerScale vectors for the quad at column n (left alone where the launch has none); returns the clamped column
+__device__ __forceinline__ int load_col_vectors(const GemmParams& p, int n, f32x4& bias_v, f32x4& cs_v) {
+  n = quad_col(p, n);
+  if (p.bias) bias_v = *reinterpret_cast<const f32x4*>(p.bias + n);
+  if (p.colscale) cs_v = *reinterpret_cast<const f32x4*>(p.colscale + n);
+  return n;
+}
+// operands and C / R offsets of batch blockIdx.z = b1 * nb2 + b2 (b2divB consecutive b2 share one B). Declares A_, B_, COFF_, ROFF_;
+// textual (see VQ3_STAGED_EPILOGUE_RM: the function forms, by reference or by value, moved instructions in the f32 kernels of gemm2.hip)
+#define VQ3_BATCH_OPERANDS(P_, A_, B_, COFF_, ROFF_)                            \
+  const int b1 = blockIdx.z / (P_).nb2, b2 = blockIdx.z % (P_).nb2;             \
+  const bf16_t* A_ = (P_).A + b1 * (P_).sA1 + b2 * (P_).sA2;                    \
+  const bf16_t* B_ = (P_).B + b1 * (P_).sB1 + (long)(b2 / (P_).b2divB) * (P_).sB2; \
+  const long COFF_ = b1 * (P_).sC1 + b2 * (P_).sC2;                             \
+  const long ROFF_ = b1 * (P_).sR1 + b2 * (P_).sR2
 __device__ __forceinline__ f32x4 ln_apply(const f32x4& a, float mu, float rs, const f32x4& c) {
   f32x4 o;
 #pragma unroll
@@ -378,14 +398,15 @@ __device__ __forceinline__ void stage_quad(const GemmParams& p, char* smem, int 
   *reinterpret_cast<u32x2*>(smem + cstage_off<BN>(ml, nl >> 3) + ((nl & 4) << 1)) = o;
 }
 // the (ACT, MODE) pairs the launches of a step use get a compiled form each; anything else takes the run-time form
-#define VQ3_STAGE_DISPATCH(P, CALL)                                                                           \
+// (CALL(ACT, MODE, whatever follows CALL in the dispatch's own arguments))
+#define VQ3_STAGE_DISPATCH(P, CALL, ...)                                                                      \
   do {                                                                                                        \
     const int mode__ = ((P).bias ? 1 : 0) | ((P).colscale ? 2 : 0) | ((P).alpha != 1.f ? 4 : 0);              \
-    if ((P).act == 0 && mode__ == 0) CALL(0, 0);                                                              \
-    else if ((P).act == 0 && mode__ == 1) CALL(0, 1);                                                         \
-    else if ((P).act == 1 && mode__ == 1) CALL(1, 1);                                                         \
-    else if ((P).act == 0 && mode__ == 3) CALL(0, 3);                                                         \
-    else CALL(-1, -1);                                                                                        \
+    if ((P).act == 0 && mode__ == 0) CALL(0, 0, ##__VA_ARGS__);                                               \
+    else if ((P).act == 0 && mode__ == 1) CALL(0, 1, ##__VA_ARGS__);                                          \
+    else if ((P).act == 1 && mode__ == 1) CALL(1, 1, ##__VA_ARGS__);                                          \
+    else if ((P).act == 0 && mode__ == 3) CALL(0, 3, ##__VA_ARGS__);                                          \
+    else CALL(-1, -1, ##__VA_ARGS__);                                                                         \
   } while (0)
 
 template <int BM, int BN>
@@ -747,6 +768,112 @@ __device__ __forceinline__ bool staged_ok(const GemmParams& p, long coff, long r
          (!p.R || ((p.ldr % 8 == 0) && (roff % 8 == 0) && ((reinterpret_cast<uintptr_t>(p.R) & 15) == 0)));
 }
 
+// ---- the epilogue of the row-major wave layout (gemm2.hip, gemm3.hip) ---------------------------------------------------------
+// WM x WN compute waves, wave (wm, wn) owns a (BM / WM) x (BN / WN) block as TM x TN MFMA tiles of 16 x 16; lane (fr, fq) = (lane & 15,
+// lane >> 4) holds row fr, columns 4 fq .. 4 fq + 3 of each. Staged form, in order:
+//   column vectors (global loads)  ->  __syncthreads: every wave's fragment reads of the last stage are done, the LDS is free
+//   [folded LayerNorm: (mu, rstd) pairs to LDS -> __syncthreads -> each lane reads its rows' pairs -> __syncthreads (before the C image
+//    overwrites the pairs) -> rstd (acc - mu c) per lane-owned row]
+//   stage_quad per quad into the C image  ->  __syncthreads  ->  staged_store: whole rows out
+// Every hand-off is a __syncthreads(), which waits for the wave's own LDS traffic before the barrier. Loader waves have returned.
+// TEXTUAL on purpose: written as __forceinline__ function templates these three re-allocated registers in every kernel that used them
+// (gemm2.hip: 120 -> 127, 146 -> 167, 179 -> 194 VGPRs), expanded in place they leave the generated code as it was. They expand inside a
+// kernel of this layout and use its names: p, smem, acc[TM][TN], the extents BM BN WM WN TM TN NW, wm wn fr fq tid, m0 n0 coff roff and
+// the early statistics ln_mu ln_rs (ln_row_early).
+#define VQ3_STAGE_RM(ACT_, MODE_)                                                                                                   \
+  do {                                                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                                  \
+      _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                                                \
+        stage_quad<BN, ACT_, MODE_>(p, smem, wm * (BM / WM) + i * 16 + fr, wn * (BN / WN) + j * 16 + 4 * fq, acc[i][j], bias_v[j], cs_v[j]); \
+  } while (0)
+#define VQ3_STAGED_EPILOGUE_RM()                                                                                                    \
+  do {                                                                                                                              \
+    f32x4 bias_v[TN], cs_v[TN];                                                                                                     \
+    _Pragma("unroll") for (int j = 0; j < TN; ++j) load_col_vectors(p, n0 + wn * (BN / WN) + j * 16 + 4 * fq, bias_v[j], cs_v[j]);  \
+    __syncthreads();                                                                                                                \
+    if (p.ln_in) {                                                                                                                  \
+      f32x4 cc[TN];                                                                                                                 \
+      float mu[TM], rs[TM];                                                                                                         \
+      _Pragma("unroll") for (int j = 0; j < TN; ++j) cc[j] = ln_colsum(p, n0 + wn * (BN / WN) + j * 16 + 4 * fq);                   \
+      if (tid < BM) reinterpret_cast<float2*>(smem)[tid] = float2{ln_mu, ln_rs};                                                    \
+      __syncthreads();                                                                                                              \
+      _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                              \
+        const float2 v = reinterpret_cast<const float2*>(smem)[wm * (BM / WM) + i * 16 + fr];                                       \
+        mu[i] = v.x; rs[i] = v.y;                                                                                                   \
+      }                                                                                                                             \
+      __syncthreads();                                                                                                              \
+      _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                                \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] = ln_apply(acc[i][j], mu[i], rs[i], cc[j]);                        \
+    }                                                                                                                               \
+    VQ3_STAGE_DISPATCH(p, VQ3_STAGE_RM);                                                                                            \
+    __syncthreads();                                                                                                                \
+    staged_store<BM, BN>(p, smem, coff, roff, m0, n0, tid, 64 * NW);                                                                \
+  } while (0)
+// un-staged form: the quads whose row and first column lie inside C. ROW_ / COL_: global row of the lane's i-th MFMA tile row / first
+// global column of its j-th quad (expressions in i / j); the rest: what stores quad (i, j) at (m, n) - store_quad and its kin
+#define VQ3_DIRECT_STORE(TM_, TN_, ROW_, COL_, ...)               \
+  do {                                                            \
+    _Pragma("unroll") for (int i = 0; i < (TM_); ++i) {           \
+      const int m = (ROW_);                                       \
+      if (m >= p.M) continue;                                     \
+      _Pragma("unroll") for (int j = 0; j < (TN_); ++j) {         \
+        const int n = (COL_);                                     \
+        if (n >= p.N) continue;                                   \
+        __VA_ARGS__;                                              \
+      }                                                           \
+    }                                                             \
+  } while (0)
+
+// EK kernels (gemm6.hip, gemm7.hip: one instantiation per epilogue kind EK_): activation, bias / LayerScale / alpha and the LayerNorm
+// fold (LN_ON_: run time, for EK 1) are dispatched ONCE per tile to STAGE_ALL_(act tag, mode tag, fold tag), the kernel's own loop over its
+// quads (the accumulator indexing differs). The fused q|k|v and SwiGLU epilogues never carry an activation or LayerScale (SwiGLU - host:
+// no bias and alpha == 1 either).
+#define VQ3_STAGE_EK(ACT_, MODE_, EK_, LN_ON_, STAGE_ALL_)                                                                          \
+  do {                                                                                                                              \
+    if constexpr ((EK_) == 3) STAGE_ALL_(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{}); \
+    else if constexpr ((EK_) == 1) {                                                                                                \
+      if (LN_ON_) STAGE_ALL_(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::true_type{});          \
+      else STAGE_ALL_(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});                \
+    } else STAGE_ALL_(std::integral_constant<int, ACT_>{}, std::integral_constant<int, MODE_>{}, std::false_type{});                \
+  } while (0)
+#define VQ3_STAGE_DISPATCH_EK(P, EK_, LN_ON_, STAGE_ALL_)                                  \
+  do {                                                                                     \
+    if constexpr ((EK_) == 2 || (EK_) == 4) VQ3_STAGE_EK(0, 0, EK_, LN_ON_, STAGE_ALL_);   \
+    else if constexpr ((EK_) == 1) {                                                       \
+      if ((P).bias && (P).alpha == 1.f) VQ3_STAGE_EK(0, 1, EK_, LN_ON_, STAGE_ALL_);       \
+      else VQ3_STAGE_EK(0, -1, EK_, LN_ON_, STAGE_ALL_);                                   \
+    } else VQ3_STAGE_DISPATCH(P, VQ3_STAGE_EK, EK_, LN_ON_, STAGE_ALL_);                   \
+  } while (0)
+
+// ---- loader-wave ring (gemm2.hip, gemm3.hip, gemm_fp8.hip): what a dedicated DMA wave runs instead of the main loop ------------
+// The ring runs NSTAGE - 1 K tiles ahead (cold, HBM-resident weights need more than two tiles of latency cover). Per K step: wait until
+// this wave's PPW pieces of tile t have landed (counted vmcnt: up to NSTAGE - 2 younger tiles stay in flight), meet the compute waves at
+// the step's ONE raw s_barrier - the LDS is written by DMA only, retired by that vmcnt, so the barrier needs no lgkmcnt wait - and request
+// tile t + NSTAGE - 1 into the stage tile t - 1 was read from (its readers passed this barrier after their MFMAs were issued).
+// NSTAGE_ / PPW_: compile-time constants (the wait counts are immediates); NT_: K tiles; ISSUE_(tile, stage) requests this wave's pieces
+// of one K tile. Textual for the same reason as the epilogue above (as a function template: 2-5 instructions more per kernel).
+#define VQ3_LOADER_RING(NSTAGE_, PPW_, NT_, ISSUE_)                                                                          \
+  do {                                                                                                                       \
+    static_assert(((NSTAGE_) - 2 > 3 ? 3 : (NSTAGE_) - 2) * (PPW_) < 64, "the wait counts fit vmcnt's 6 bits");              \
+    const int ring_last = (NT_) - 1;                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < (NSTAGE_) - 1; ++i)                                                                \
+      if (i < (NT_)) ISSUE_(i, i);                                                                                           \
+    int stage = 0;                                                                                                           \
+    for (int t = 0; t <= ring_last; ++t) {                                                                                   \
+      const int newer = (ring_last - t) < ((NSTAGE_) - 2) ? (ring_last - t) : ((NSTAGE_) - 2); /* tiles that stay in flight */ \
+      if ((NSTAGE_) > 4 && newer >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (PPW_)) : "memory");                     \
+      else if (newer == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PPW_)) : "memory");                                 \
+      else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW_) : "memory");                                       \
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                  \
+      __builtin_amdgcn_s_barrier();                                                                                          \
+      if (t + (NSTAGE_) - 1 <= ring_last) {                                                                                  \
+        int s2 = stage + (NSTAGE_) - 1; s2 = s2 >= (NSTAGE_) ? s2 - (NSTAGE_) : s2;                                          \
+        ISSUE_(t + (NSTAGE_) - 1, s2);                                                                                       \
+      }                                                                                                                      \
+      stage = stage == (NSTAGE_) - 1 ? 0 : stage + 1;                                                                        \
+    }                                                                                                                        \
+  } while (0)
+
 // host twin of staged_ok for every batch index (the v6 kernels compile ONLY the staged bf16 epilogue: gemm6.hip routes the rest elsewhere)
 inline bool host_staged_ok(const GemmParams& p) {
   return !p.out_f32 && p.nsplit == 1 && p.vec_ok && (p.ldc % 8 == 0) && (p.sC1 % 8 == 0) && (p.sC2 % 8 == 0) &&
@@ -801,6 +928,38 @@ inline void choose_tile_order(GemmParams& p, int BM, int BN, int wg_per_cu) {
     }
   }
   p.xm = bxm; p.nbw = bnb;
+}
+
+// host: what every launcher does before it launches. Kernels... are the instantiations the launcher may pick from (they share one
+// dynamic LDS size): their limit is raised once per process, on the first call for this set of symbols. 0, or 2 with the error text set.
+template <auto... Kernels>
+int set_dynamic_lds(const char* family, int smem) {
+  static bool attr_done = false;
+  if (attr_done) return 0;
+  hipError_t e = hipSuccess;
+  ((e = e != hipSuccess ? e : hipFuncSetAttribute((const void*)Kernels, hipFuncAttributeMaxDynamicSharedMemorySize, smem)), ...);
+  if (e != hipSuccess) {
+    vq3_set_error("%s: hipFuncSetAttribute failed: %s", family, hipGetErrorString(e));
+    return 2;
+  }
+  attr_done = true;
+  return 0;
+}
+// ... and the tile grid of BM x BN tiles with its XCD order (wg_per_cu: workgroups that share a CU, for choose_tile_order's traffic model)
+template <auto... Kernels>
+int prepare_launch(GemmParams& p, const char* family, int smem, int BM, int BN, int wg_per_cu) {
+  if (int rc = set_dynamic_lds<Kernels...>(family, smem)) return rc;
+  p.mtiles = (p.M + BM - 1) / BM;
+  p.ntiles = (p.N + BN - 1) / BN;
+  choose_tile_order(p, BM, BN, wg_per_cu);
+  return 0;
+}
+// host: C (and R) rows, batch offsets included, take 4-wide stores (GemmParams::vec_ok)
+inline bool host_vec_ok(const GemmParams& p) {
+  const int esz = p.out_f32 ? 4 : 2;
+  bool vec = (p.ldc % 4 == 0) && (p.sC1 % 4 == 0) && (p.sC2 % 4 == 0) && ((uintptr_t)p.C % (4 * esz) == 0);
+  if (p.R) vec = vec && (p.ldr % 4 == 0) && (p.sR1 % 4 == 0) && (p.sR2 % 4 == 0) && ((uintptr_t)p.R % (4 * esz) == 0);
+  return vec;
 }
 
 // v2 (LDS-DMA pipelined) launcher, defined in gemm2.hip. cfg: one of gemm_config.h's CFG_V2_* ids; -1 (nothing launched) for any other.

@@ -38,7 +38,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (WM * WN + NLOAD + 3) / 4) 
   const char* A = reinterpret_cast<const char*>(p.A);
   const char* B = reinterpret_cast<const char*>(p.B);
   const int nt = p.K / BKB;
-  const int last = nt - 1;
 
   if (loader) {
     const int prow = lane >> 3;
@@ -65,23 +64,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (WM * WN + NLOAD + 3) / 4) 
                                          (__attribute__((address_space(3))) void*)(sb + pi * 1024), 16, 0, 0);
       }
     };
-#pragma unroll
-    for (int i = 0; i < NSTAGE - 1; ++i)
-      if (i < nt) issue(i, i);
-    int stage = 0;
-    for (int t = 0; t < nt; ++t) {
-      const int newer = (last - t) < (NSTAGE - 2) ? (last - t) : (NSTAGE - 2);
-      if (newer >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PPW) : "memory");
-      else if (newer == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
-      else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (t + NSTAGE - 1 <= last) {
-        int s2 = stage + NSTAGE - 1; s2 = s2 >= NSTAGE ? s2 - NSTAGE : s2;
-        issue(t + NSTAGE - 1, s2);
-      }
-      stage = stage == NSTAGE - 1 ? 0 : stage + 1;
-    }
+    VQ3_LOADER_RING(NSTAGE, PPW, nt, issue);
     return;
   }
 
@@ -152,22 +135,20 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), (WM * WN + NLOAD + 3) / 4) 
 template <int BM, int BN, int WM, int WN, int NSTAGE, int NLOAD>
 int launch_fp8(GemmParams& p, const float* rs, const float* cs, hipStream_t stream) {
   constexpr int SMEM = NSTAGE * (BM + BN) * 128;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_fp8_kernel<BM, BN, WM, WN, NSTAGE, NLOAD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) {
-      vq3_set_error("gemm fp8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
-  p.mtiles = (p.M + BM - 1) / BM;
-  p.ntiles = (p.N + BN - 1) / BN;
-  choose_tile_order(p, BM, BN, 1);
+  if (int rc = prepare_launch<gemm_fp8_kernel<BM, BN, WM, WN, NSTAGE, NLOAD>>(p, "gemm fp8", SMEM, BM, BN, 1)) return rc;
   hipLaunchKernelGGL((gemm_fp8_kernel<BM, BN, WM, WN, NSTAGE, NLOAD>), dim3(p.mtiles * p.ntiles), dim3(64 * (WM * WN + NLOAD)),
                      SMEM, stream, p, rs, cs);
   return 0;
+}
+
+// an e4m3 product as GemmParams (one batch, bf16 C, bytes where the bf16 kernels count elements); vec_ok is the caller's, once C is final
+GemmParams fp8_params(const void* Xq, const void* Wq, void* C, const void* residual, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldc,
+                      int64_t ldr) {
+  GemmParams p{};
+  p.A = (const bf16_t*)Xq; p.B = (const bf16_t*)Wq; p.C = C; p.R = residual;
+  p.M = M; p.N = N; p.K = K; p.lda = (int)ldx; p.ldb = (int)ldw; p.ldc = (int)ldc; p.ldr = (int)ldr;
+  p.nb2 = 1; p.b2divB = 1; p.kper = K; p.nsplit = 1; p.alpha = 1.0f;
+  return p;
 }
 
 // ---------------------------------------------------------------------------------------------------- quantisation
@@ -280,11 +261,8 @@ extern "C" int vq3_gemm_fp8_nt(const void* Xq, const float* x_scale, const void*
   VQ3_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 128 == 0, "gemm_fp8: need K %% 128 == 0 (M=%d N=%d K=%d)", M, N, K);
   VQ3_CHECK_ARG(ldx >= K && ldw >= K && ldx % 16 == 0 && ldw % 16 == 0 && ldc >= N, "gemm_fp8: bad leading dimensions");
   VQ3_CHECK_ARG((uintptr_t)Xq % 16 == 0 && (uintptr_t)Wq % 16 == 0, "gemm_fp8: operands must be 16-byte aligned");
-  GemmParams p{};
-  p.A = (const bf16_t*)Xq; p.B = (const bf16_t*)Wq; p.C = C; p.R = residual;
-  p.M = M; p.N = N; p.K = K; p.lda = (int)ldx; p.ldb = (int)ldw; p.ldc = (int)ldc; p.ldr = (int)ldr;
-  p.nb2 = 1; p.b2divB = 1; p.kper = K; p.nsplit = 1; p.alpha = 1.0f;
-  p.vec_ok = (ldc % 4 == 0 && (uintptr_t)C % 8 == 0 && (!residual || (ldr % 4 == 0 && (uintptr_t)residual % 8 == 0))) ? 1 : 0;
+  GemmParams p = fp8_params(Xq, Wq, C, residual, M, N, K, ldx, ldw, ldc, ldr);
+  p.vec_ok = host_vec_ok(p) ? 1 : 0;
   // 256x128 tiles halve the L2 -> LDS bytes per FLOP (the fp8 MFMA rate makes the 128x128 tile L2-bound); they pay off
   // once the grid still fills the chip
   static int force = -1;
@@ -370,10 +348,7 @@ extern "C" int vq3_gemm_fp8_ex(const vq3_gemm_fp8_desc* d, void* stream) {
     VQ3_CHECK_ARG(d->C != nullptr, "gemm_fp8_ex: null output");
     if (d->w_scale) return vq3_gemm_fp8_nt(d->Xq, d->x_scale, d->Wq, d->w_scale, d->C, d->residual, d->M, d->N, d->K, d->ldx, d->ldw, d->ldc, d->ldr, stream);
   }
-  GemmParams p{};
-  p.A = (const bf16_t*)d->Xq; p.B = (const bf16_t*)d->Wq; p.C = d->C; p.R = d->residual;
-  p.M = d->M; p.N = d->N; p.K = d->K; p.lda = (int)d->ldx; p.ldb = (int)d->ldw; p.ldc = (int)d->ldc; p.ldr = (int)d->ldr;
-  p.nb2 = 1; p.b2divB = 1; p.kper = d->K; p.nsplit = 1; p.alpha = 1.0f;
+  GemmParams p = fp8_params(d->Xq, d->Wq, d->C, d->residual, d->M, d->N, d->K, d->ldx, d->ldw, d->ldc, d->ldr);
   p.f8_rs = d->x_scale; p.f8_cs = d->w_scale;
   if (d->mode == 1) {
     VQ3_CHECK_ARG(d->C && d->N % 256 == 0 && d->ldc >= d->N / 2 && d->ldc % 8 == 0 && !d->residual, "gemm_fp8_ex: SwiGLU forward needs N = 2 I, I %% 128 == 0");
@@ -385,7 +360,7 @@ extern "C" int vq3_gemm_fp8_ex(const vq3_gemm_fp8_desc* d, void* stream) {
     p.epi = 2; p.sw_gu = (const bf16_t*)d->gu; p.sw_dgu = (bf16_t*)d->dgu;
     p.C = d->dgu; p.ldc = d->N;            // placeholders (alignment checks only)
   }
-  p.vec_ok = (p.ldc % 4 == 0 && (uintptr_t)p.C % 8 == 0 && (!p.R || (p.ldr % 4 == 0 && (uintptr_t)p.R % 8 == 0))) ? 1 : 0;
+  p.vec_ok = host_vec_ok(p) ? 1 : 0;
   const int rc = launch_gemm_v6_f8(p, (hipStream_t)stream);
   if (rc > 0) return rc;
   if (rc == 0) {
