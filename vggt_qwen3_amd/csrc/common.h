@@ -129,6 +129,11 @@ __device__ __forceinline__ float gelu_erf_b(float x) { return gelu_erf2_b(f32x2_
 // unfused forms of an op stay bit-identical to each other.
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
+// d(silu(g) * u) / dg * d = d * u * sigma * (1 + g * (1 - sigma)), sg = sigmoid_f(g). The bounded factor (|sigma (1 + g (1 - sigma))| <= 1.1)
+// is multiplied in first: d * u formed first overflows to inf for huge d and u, and inf times a sigmoid that v_rcp_f32 flushed to 0
+// (g < -87) is NaN where the true gradient is 0. (u * factor can itself overflow only for |u| within 10 % of the f32 maximum.)
+// Shared by the stand-alone kernel and the GEMM epilogue so the two stay bit-identical.
+__device__ __forceinline__ float swiglu_dgate_f(float d, float u, float g, float sg) { return d * (u * (sg * (1.f + g * (1.f - sg)))); }
 
 // Counter-based dropout decision (vq3_dropout, the fused Perceiver cross-attention): 24 uniform bits from (seed, element index);
 // an element is kept when they are >= (unsigned)(p * 2^24). Stateless, so a re-run with the same (seed, offset) repeats the mask.

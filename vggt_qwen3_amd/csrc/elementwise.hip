@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void silu_mul_bwd_kernel(const bf16_t* __restr
       const float gf = bf2f((bf16_t)g[j]), uf = bf2f((bf16_t)u[j]), df = bf2f((bf16_t)d[j]);
       const float sg = sigmoid_f(gf);
       const float sl = gf * sg;
-      og[j] = (short)f2bf(df * uf * (sg * (1.f + gf * (1.f - sg))));
+      og[j] = (short)f2bf(swiglu_dgate_f(df, uf, gf, sg));
       ou[j] = (short)f2bf(df * sl);
     }
     *reinterpret_cast<bf16x8*>(dgu + r * 2L * inter + c) = og;

@@ -520,7 +520,7 @@ __device__ __forceinline__ void staged_store(const GemmParams& p, const char* sm
             const float gf = bf2f((bf16_t)((gv[u][k] >> (16 * hgh)) & 0xffff));
             const float uf = bf2f((bf16_t)((uv[u][k] >> (16 * hgh)) & 0xffff));
             const float sg = sigmoid_f(gf);
-            r_g[hgh] = df * uf * (sg * (1.f + gf * (1.f - sg)));
+            r_g[hgh] = swiglu_dgate_f(df, uf, gf, sg);
             r_u[hgh] = df * (gf * sg);
           }
           og[k] = pack2bf(r_g[0], r_g[1]);

@@ -206,7 +206,13 @@ def rmsnorm_fwd(x: torch.Tensor, w: torch.Tensor, eps: float, want_rstd: bool = 
     _req(x, BF16, "rmsnorm x"); _req(w, BF16, "rmsnorm w")
     assert x.dim() == 2 and x.stride(1) == 1
     rows, cols = x.shape
-    y = _out2d(out, rows, cols, x, "rmsnorm_fwd")
+    if out is not None and out.dim() == 2 and out.stride(1) == 1 and out.stride(0) > cols:
+        # a column block of a wider slab: the kernel takes the row stride (ldy), as it does for x
+        if out.dtype != BF16 or tuple(out.shape) != (rows, cols) or out.device != x.device:
+            raise _lib.Vq3Error(f"rmsnorm_fwd: out must be a bf16 [{rows}, {cols}] tensor with unit column stride on {x.device}")
+        y = out
+    else:
+        y = _out2d(out, rows, cols, x, "rmsnorm_fwd")
     rstd = torch.empty((rows,), device=x.device, dtype=F32) if want_rstd else None
     check(_lib.load().vq3_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), _p(rstd), rows, cols, x.stride(0),
                                       y.stride(0), eps, _stream()), "vq3_rmsnorm_fwd")
