@@ -384,7 +384,7 @@ int vq3_pack_tokens(const int32_t* prompt_ids, const int32_t* prompt_off, const 
  * All per-step state (lens, step, generated, finished) is read from DEVICE memory so a step can be graph-replayed.
  * ---------------------------------------------------------------------------------------------------------- */
 /* y[M, N] = f(x)[M, K] . W[N, K]^T (+ residual[M, N] bf16), 1 <= M <= 8: the weight-streaming (HBM-bound) form of
- * nn.Linear for one token per row. x, W bf16, K % 8 == 0; y bf16 (or f32 if out_f32). xmode selects f:
+ * nn.Linear for one token per row (csrc/skinny_gemm.hip). x, W bf16, K % 8 == 0; y bf16 (or f32 if out_f32). xmode selects f:
  *   0  f(x) = x
  *   1  f(x) = ln_w * bf16(x * rsqrt(mean(x^2) + eps))       Qwen3RMSNorm (modeling_qwen3.py:49-64) fused in
  *   2  f(x) = bf16(bf16(silu(x[:, :K])) * x[:, K:2K])        SwiGLU (modeling_qwen3.py:81-83) fused into down_proj */

@@ -36,6 +36,13 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
 __device__ __forceinline__ f32x2_t unpack2bf(uint32_t u) {
   return f32x2_t{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
 }
+// one 16-byte piece of 8 bf16 -> 8 floats
+__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
+  f[0] = __builtin_bit_cast(float, v.x << 16); f[1] = __builtin_bit_cast(float, v.x & 0xffff0000u);
+  f[2] = __builtin_bit_cast(float, v.y << 16); f[3] = __builtin_bit_cast(float, v.y & 0xffff0000u);
+  f[4] = __builtin_bit_cast(float, v.z << 16); f[5] = __builtin_bit_cast(float, v.z & 0xffff0000u);
+  f[6] = __builtin_bit_cast(float, v.w << 16); f[7] = __builtin_bit_cast(float, v.w & 0xffff0000u);
+}
 // a pair rounded through bf16 (three instructions: the conversion, a shift and a mask)
 __device__ __forceinline__ f32x2_t rbf2(f32x2_t v) {
   const uint32_t u = pack2bf(v[0], v[1]);

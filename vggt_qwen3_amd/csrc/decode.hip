@@ -1,13 +1,11 @@
 // Greedy decoding for Qwen3 with a resident KV cache (the reference's inference callers:
 // src/inference/qa_inference.py:207-216, arkit_inference.py:274-284 -> transformers generate(), greedy, with
-// repetition_penalty and no_repeat_ngram_size). One new token per row and step, so every contraction is a
-// matrix-vector product that streams the weights once: HBM-bound, not MFMA-bound.
+// repetition_penalty and no_repeat_ngram_size). The projections of a step are the skinny GEMMs of skinny_gemm.hip; this
+// file holds what runs between them.
 //
 // All step state lives in device memory (per-row cache lengths, step counter, generated ids, finished flags), so one
 // decode step is a fixed sequence of launches with fixed arguments - capturable in a HIP graph and replayed per token.
 //
-//  * vq3_skinny_gemm_bf16   y[M<=8, N] = x W^T (+ residual): a wave owns 4 weight rows, lanes stride K in 16-byte
-//                           pieces (coalesced 1 KiB per row per load), fp32 accumulation, wave reduction at the end.
 //  * vq3_qwen_decode_qkprep q/k RMSNorm + RoPE at position lens[b], K and V written straight into the cache slot.
 //  * vq3_qwen_decode_attn   softmax(q K^T / sqrt(D)) V over the row's lens[b]+1 cached positions, GQA by indexing.
 //  * vq3_greedy_pick        repetition penalty -> n-gram ban -> argmax -> eos/pad bookkeeping, one workgroup per row.
@@ -18,392 +16,6 @@
 namespace {
 
 constexpr int D = 128;
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
-  f[0] = __builtin_bit_cast(float, v.x << 16); f[1] = __builtin_bit_cast(float, v.x & 0xffff0000u);
-  f[2] = __builtin_bit_cast(float, v.y << 16); f[3] = __builtin_bit_cast(float, v.y & 0xffff0000u);
-  f[4] = __builtin_bit_cast(float, v.z << 16); f[5] = __builtin_bit_cast(float, v.z & 0xffff0000u);
-  f[6] = __builtin_bit_cast(float, v.w << 16); f[7] = __builtin_bit_cast(float, v.w & 0xffff0000u);
-}
-
-// ------------------------------------------------------------------------------------------------ skinny GEMM
-// XMODE 0: x as given. 1: x = ln_w * bf16(x * rstd(x)) (Qwen3RMSNorm fused into the consumer; every wave recomputes the
-// row statistics from the K-element rows, which sit in L2). 2: x = bf16(silu(gate) * up) with gate = xin[:, :K],
-// up = xin[:, K:2K] (SwiGLU fused into down_proj).
-template <int MT, int R, int XMODE>
-__global__ __launch_bounds__(256) void skinny_gemm_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
-                                                         void* __restrict__ y, const bf16_t* __restrict__ res,
-                                                         const bf16_t* __restrict__ ln_w, float eps, int M, int N, int K,
-                                                         long ldx, long ldw, long ldy, long ldr, int out_f32) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int n0 = (blockIdx.x * 4 + wid) * R;
-  if (n0 >= N) return;
-  float rstd[MT];
-  if (XMODE == 1) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float ss = 0.f;
-      const bf16_t* xr = x + (long)min(m, M - 1) * ldx;
-      for (int k = lane * 8; k < K; k += 512) {
-        float f[8];
-        unpack8(*(const u32x4*)(xr + k), f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ss = fmaf(f[j], f[j], ss);
-      }
-      rstd[m] = rsqrtf(wave_sum(ss) / (float)K + eps);
-    }
-  }
-  float acc[R][MT];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
-  const bf16_t* wrow[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) wrow[r] = W + (long)min(n0 + r, N - 1) * ldw;
-  constexpr int U = R >= 4 ? 1 : (R == 2 ? 2 : 4);   // K chunks in flight: R * U 16-byte weight loads per lane
-  for (int k0 = lane * 8; k0 < K; k0 += 512 * U) {   // K % 8 == 0
-    u32x4 wv[U][R];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = min(k0 + 512 * u, K - 8);        // clamped duplicate loads are masked below
-#pragma unroll
-      for (int r = 0; r < R; ++r) wv[u][r] = __builtin_nontemporal_load((const u32x4*)(wrow[r] + k));
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = k0 + 512 * u;
-      if (k >= K) break;
-      float xf[MT][8];
-      float lw[8];
-      if (XMODE == 1) unpack8(*(const u32x4*)(ln_w + k), lw);
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const bf16_t* xr = x + (long)min(m, M - 1) * ldx;
-        unpack8(*(const u32x4*)(xr + k), xf[m]);
-        if (XMODE == 1) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xf[m][j] = rbf(lw[j] * rbf(xf[m][j] * rstd[m]));
-        } else if (XMODE == 2) {
-          float up[8];
-          unpack8(*(const u32x4*)(xr + K + k), up);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float g = xf[m][j];
-            xf[m][j] = rbf(rbf(silu_f(g)) * up[j]);
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        float wf[8];
-        unpack8(wv[u][r], wf);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[r][m] = fmaf(wf[j], xf[m][j], acc[r][m]);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const float s = wave_sum(acc[r][m]);
-      if (lane == 0 && m < M && n0 + r < N) {
-        float v = s;
-        if (res) v = rbf(v) + bf2f(res[(long)m * ldr + n0 + r]);   // GEMM output is bf16 before the residual add
-        if (out_f32) ((float*)y)[(long)m * ldy + n0 + r] = v;
-        else ((bf16_t*)y)[(long)m * ldy + n0 + r] = f2bf(v);
-      }
-    }
-}
-
-// Register-resident-x variant for 1-2 rows (the reference's callers decode one prompt at a time): a block of 4 waves is
-// split into 4/KS row groups x KS K-slices (512-element chunks interleaved across the slices). Each wave loads its slice
-// of x ONCE (<= CH chunks, transformed in registers: RMSNorm statistics are combined across the slices through LDS;
-// SwiGLU is evaluated once per wave), then streams R weight rows with all R*CH 16-byte loads of a row group in
-// flight before the first FMA. More waves per weight byte than the generic kernel -> enough loads in flight to
-// approach HBM bandwidth at N = 2560.
-template <int MT, int R, int KS, int XMODE>
-__global__ __launch_bounds__(256) void skinny_regx_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
-                                                         void* __restrict__ y, const bf16_t* __restrict__ res,
-                                                         const bf16_t* __restrict__ ln_w, float eps, int M, int N, int K,
-                                                         long ldx, long ldw, long ldy, long ldr, int out_f32) {
-  constexpr int CH = 5;
-  constexpr int G = 4 / KS;
-  __shared__ float red[4][MT];
-  __shared__ float part[4][R][MT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g = wid / KS, ks = wid % KS;
-  const int n0 = (blockIdx.x * G + g) * R;
-  float xf[MT][CH][8];
-  int kof[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) kof[c] = (c * KS + ks) * 512 + lane * 8;
-  // the weight stream does not depend on x: put all of this wave's weight loads in flight first, then prepare x under them
-  const bool active = n0 < N;
-  u32x4 wv[R][CH];
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const bf16_t* wr = W + (long)min(n0 + r, N - 1) * ldw;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) wv[r][c] = __builtin_nontemporal_load((const u32x4*)(wr + min(kof[c], K - 8)));
-    }
-  }
-  u32x4 lwv[CH];
-  if (XMODE == 1) {
-#pragma unroll
-    for (int c = 0; c < CH; ++c) lwv[c] = *(const u32x4*)(ln_w + min(kof[c], K - 8));
-  }
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const bf16_t* xr = x + (long)min(m, M - 1) * ldx;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      if (kof[c] < K) {
-        unpack8(*(const u32x4*)(xr + kof[c]), xf[m][c]);
-        if (XMODE == 2) {
-          float up[8];
-          unpack8(*(const u32x4*)(xr + K + kof[c]), up);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xf[m][c][j] = rbf(rbf(silu_f(xf[m][c][j])) * up[j]);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[m][c][j] = 0.f;
-      }
-    }
-  }
-  if (XMODE == 1) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float ss = 0.f;
-#pragma unroll
-      for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ss = fmaf(xf[m][c][j], xf[m][c][j], ss);
-      ss = wave_sum(ss);
-      if (lane == 0) red[wid][m] = ss;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float tot = 0.f;
-#pragma unroll
-      for (int q = 0; q < KS; ++q) tot += red[g * KS + q][m];
-      const float rstd = rsqrtf(tot / (float)K + eps);
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        if (kof[c] < K) {
-          float lw[8];
-          unpack8(lwv[c], lw);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xf[m][c][j] = rbf(lw[j] * rbf(xf[m][c][j] * rstd));
-        }
-      }
-    }
-  }
-  float acc[R][MT];
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        float wf[8];
-        unpack8(wv[r][c], wf);          // chunks past K meet x == 0
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[r][m] = fmaf(wf[j], xf[m][c][j], acc[r][m]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        acc[r][m] = wave_sum(acc[r][m]);
-        if (KS > 1 && lane == 0) part[wid][r][m] = acc[r][m];
-      }
-  }
-  if (KS > 1) __syncthreads();
-  if (n0 >= N || ks != 0 || lane != 0) return;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      if (m >= M || n0 + r >= N) continue;
-      float v = acc[r][m];
-#pragma unroll
-      for (int q = 1; q < KS; ++q) v += part[wid + q][r][m];
-      if (res) v = rbf(v) + bf2f(res[(long)m * ldr + n0 + r]);
-      if (out_f32) ((float*)y)[(long)m * ldy + n0 + r] = v;
-      else ((bf16_t*)y)[(long)m * ldy + n0 + r] = f2bf(v);
-    }
-}
-
-// e4m3 weights (config C5): the same register-resident-x scheme with 16-byte pieces = 16 weights. The activation row is
-// quantised per token exactly as the fp8 GEMM does (amax over the whole row -> e4m3 round trip in registers), so decode
-// and prefill follow one numeric contract; the weight stream - the only thing that costs time here - is halved.
-__device__ __forceinline__ void unpack16_fp8(const u32x4 v, float* f) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], false);
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], true);
-    f[4 * w + 0] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
-  }
-}
-
-template <int MT, int R, int KS, int XMODE>
-__global__ __launch_bounds__(256) void skinny_fp8_kernel(const bf16_t* __restrict__ x, const uint8_t* __restrict__ W,
-                                                        const float* __restrict__ wscale, bf16_t* __restrict__ y,
-                                                        const bf16_t* __restrict__ res, const bf16_t* __restrict__ ln_w,
-                                                        float eps, int M, int N, int K, long ldx, long ldw, long ldy, long ldr) {
-  constexpr int CH = 3;
-  constexpr int G = 4 / KS;
-  __shared__ float red[4][MT];
-  __shared__ float redm[4][MT];
-  __shared__ float part[4][R][MT];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g = wid / KS, ks = wid % KS;
-  const int n0 = (blockIdx.x * G + g) * R;
-  const bool active = n0 < N;
-  int kof[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) kof[c] = (c * KS + ks) * 1024 + lane * 16;
-  u32x4 wv[R][CH];
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const uint8_t* wr = W + (long)min(n0 + r, N - 1) * ldw;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) wv[r][c] = __builtin_nontemporal_load((const u32x4*)(wr + min(kof[c], K - 16)));
-    }
-  }
-  float xf[MT][CH][16];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const bf16_t* xr = x + (long)min(m, M - 1) * ldx;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      if (kof[c] < K) {
-        unpack8(*(const u32x4*)(xr + kof[c]), xf[m][c]);
-        unpack8(*(const u32x4*)(xr + kof[c] + 8), xf[m][c] + 8);
-        if (XMODE == 2) {
-          float up[16];
-          unpack8(*(const u32x4*)(xr + K + kof[c]), up);
-          unpack8(*(const u32x4*)(xr + K + kof[c] + 8), up + 8);
-#pragma unroll
-          for (int j = 0; j < 16; ++j) xf[m][c][j] = rbf(rbf(silu_f(xf[m][c][j])) * up[j]);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) xf[m][c][j] = 0.f;
-      }
-    }
-  }
-  if (XMODE == 1) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float ss = 0.f;
-#pragma unroll
-      for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) ss = fmaf(xf[m][c][j], xf[m][c][j], ss);
-      ss = wave_sum(ss);
-      if (lane == 0) red[wid][m] = ss;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float tot = 0.f;
-#pragma unroll
-      for (int q = 0; q < KS; ++q) tot += red[g * KS + q][m];
-      const float rstd = rsqrtf(tot / (float)K + eps);
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        if (kof[c] < K) {
-          float lw[16];
-          unpack8(*(const u32x4*)(ln_w + kof[c]), lw);
-          unpack8(*(const u32x4*)(ln_w + kof[c] + 8), lw + 8);
-#pragma unroll
-          for (int j = 0; j < 16; ++j) xf[m][c][j] = rbf(lw[j] * rbf(xf[m][c][j] * rstd));
-        }
-      }
-    }
-  }
-  // per-token e4m3 quantisation of the prepared row (vq3_quant_fp8_rows contract): q = e4m3(x * 448 / amax)
-  float sx[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    float am = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) am = fmaxf(am, fabsf(xf[m][c][j]));
-    am = wave_max(am);
-    if (lane == 0) redm[wid][m] = am;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    float am = 0.f;
-#pragma unroll
-    for (int q = 0; q < KS; ++q) am = fmaxf(am, redm[g * KS + q][m]);
-    const float inv = am > 0.f ? 448.0f / am : 1.0f;
-    sx[m] = am > 0.f ? am / 448.0f : 1.0f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-      for (int j = 0; j < 16; j += 2) {
-        const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(xf[m][c][j] * inv, xf[m][c][j + 1] * inv, 0, false);
-        const auto back = __builtin_amdgcn_cvt_pk_f32_fp8(pk, false);
-        xf[m][c][j] = back[0];
-        xf[m][c][j + 1] = back[1];
-      }
-  }
-  float acc[R][MT];
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        float wf[16];
-        unpack16_fp8(wv[r][c], wf);          // chunks past K meet x == 0
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) acc[r][m] = fmaf(wf[j], xf[m][c][j], acc[r][m]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        acc[r][m] = wave_sum(acc[r][m]);
-        if (KS > 1 && lane == 0) part[wid][r][m] = acc[r][m];
-      }
-  }
-  if (KS > 1) __syncthreads();
-  if (!active || ks != 0 || lane != 0) return;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      if (m >= M || n0 + r >= N) continue;
-      float v = acc[r][m];
-#pragma unroll
-      for (int q = 1; q < KS; ++q) v += part[wid + q][r][m];
-      v = rbf(v * (sx[m] * wscale[n0 + r]));
-      if (res) v += bf2f(res[(long)m * ldr + n0 + r]);
-      y[(long)m * ldy + n0 + r] = f2bf(v);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ decode q/k prep
 // grid (B, ceil(heads/4)): one head per wave; lane i holds elements i and i+64 (the rotate_half pair)
@@ -646,128 +258,7 @@ __global__ void advance_kernel(int32_t* lens, int B, int32_t* step) {
   if (step && threadIdx.x == 0) *step += 1;
 }
 
-template <int MT, int R, int XMODE>
-void launch_skinny3(const void* x, const void* W, void* y, const void* res, const void* ln_w, float eps, int M, int N, int K,
-                    long ldx, long ldw, long ldy, long ldr, int out_f32, hipStream_t s) {
-  const int blocks = (N + 4 * R - 1) / (4 * R);
-  hipLaunchKernelGGL((skinny_gemm_kernel<MT, R, XMODE>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)W,
-                     y, (const bf16_t*)res, (const bf16_t*)ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32);
-}
-template <int MT, int R>
-void launch_skinny2(int xmode, const void* x, const void* W, void* y, const void* res, const void* ln_w, float eps, int M,
-                    int N, int K, long ldx, long ldw, long ldy, long ldr, int out_f32, hipStream_t s) {
-  if (xmode == 0) launch_skinny3<MT, R, 0>(x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else if (xmode == 1) launch_skinny3<MT, R, 1>(x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else launch_skinny3<MT, R, 2>(x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-}
-template <int MT, int R, int KS>
-void launch_regx(int xmode, const void* x, const void* W, void* y, const void* res, const void* ln_w, float eps, int M, int N,
-                 int K, long ldx, long ldw, long ldy, long ldr, int out_f32, hipStream_t s) {
-  const int rows_per_block = (4 / KS) * R;
-  const dim3 grid((N + rows_per_block - 1) / rows_per_block), block(256);
-#define VQ3_REGX(XM)                                                                                                      \
-  hipLaunchKernelGGL((skinny_regx_kernel<MT, R, KS, XM>), grid, block, 0, s, (const bf16_t*)x, (const bf16_t*)W, y,        \
-                     (const bf16_t*)res, (const bf16_t*)ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32)
-  if (xmode == 0) VQ3_REGX(0);
-  else if (xmode == 1) VQ3_REGX(1);
-  else VQ3_REGX(2);
-#undef VQ3_REGX
-}
-template <int MT, int KS>
-void launch_regx_r(int xmode, const void* x, const void* W, void* y, const void* res, const void* ln_w, float eps, int M, int N,
-                   int K, long ldx, long ldw, long ldy, long ldr, int out_f32, hipStream_t s) {
-  // rows per wave: every wave keeps R * CH 16-byte loads in flight, so few waves per CU already saturate HBM; larger R
-  // divides the x traffic from L2 and the per-wave x preparation (RMSNorm / SwiGLU) by R
-  static int force = -1;
-  if (force < 0) {
-    const char* e = getenv("VQ3_SKINNY_R");
-    force = e ? atoi(e) : 0;
-  }
-  const int r = force ? force : ((xmode != 0 || (long)N * KS >= 8192) ? (N >= 1024 ? 4 : (N >= 512 ? 2 : 1)) : 1);
-  if (r >= 4) launch_regx<MT, 4, KS>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else if (r == 2) launch_regx<MT, 2, KS>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else launch_regx<MT, 1, KS>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-}
-// generic kernel: rows per wave so that enough waves cover the chip (256 CUs x >= 8 waves) before growing R
-template <int MT>
-void launch_skinny(int xmode, const void* x, const void* W, void* y, const void* res, const void* ln_w, float eps, int M,
-                   int N, int K, long ldx, long ldw, long ldy, long ldr, int out_f32, hipStream_t s) {
-  if constexpr (MT <= 2) {
-    const int chunks = (K + 511) / 512;
-    if (chunks <= 5) return launch_regx_r<MT, 1>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-    if (chunks <= 10) return launch_regx_r<MT, 2>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-    if (chunks <= 20) return launch_regx_r<MT, 4>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-    const int r = N >= 16384 ? 4 : (N >= 4096 ? 2 : 1);
-    if (r == 4) launch_skinny2<MT, 4>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-    else if (r == 2) launch_skinny2<MT, 2>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-    else launch_skinny2<MT, 1>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  } else {
-    launch_skinny2<MT, 4>(xmode, x, W, y, res, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  }
-}
-
-template <int MT, int KS>
-void launch_fp8_skinny(int xmode, const void* x, const void* W, const float* ws, void* y, const void* res, const void* ln_w,
-                       float eps, int M, int N, int K, long ldx, long ldw, long ldy, long ldr, hipStream_t s) {
-  constexpr int R = 4;
-  const int rows_per_block = (4 / KS) * R;
-  const dim3 grid((N + rows_per_block - 1) / rows_per_block), block(256);
-#define VQ3_F8(XM)                                                                                                          \
-  hipLaunchKernelGGL((skinny_fp8_kernel<MT, R, KS, XM>), grid, block, 0, s, (const bf16_t*)x, (const uint8_t*)W, ws,        \
-                     (bf16_t*)y, (const bf16_t*)res, (const bf16_t*)ln_w, eps, M, N, K, ldx, ldw, ldy, ldr)
-  if (xmode == 0) VQ3_F8(0);
-  else if (xmode == 1) VQ3_F8(1);
-  else VQ3_F8(2);
-#undef VQ3_F8
-}
-
 }  // namespace
-
-extern "C" int vq3_skinny_gemm_bf16(const void* x, const void* W, void* y, const void* residual, const void* ln_w,
-                                    float eps, int32_t xmode, int32_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw,
-                                    int64_t ldy, int64_t ldr, int32_t out_f32, void* stream) {
-  VQ3_CHECK_ARG(x && W && y, "skinny_gemm: null pointer");
-  VQ3_CHECK_ARG(M >= 1 && M <= 8, "skinny_gemm: M must be in [1, 8], got %d (use vq3_gemm_bf16_nt)", M);
-  VQ3_CHECK_ARG(N > 0 && K > 0 && K % 8 == 0, "skinny_gemm: need N > 0 and K %% 8 == 0 (N=%d K=%d)", N, K);
-  VQ3_CHECK_ARG(xmode >= 0 && xmode <= 2 && (xmode != 1 || ln_w), "skinny_gemm: xmode must be 0, 1 (needs ln_w) or 2");
-  VQ3_CHECK_ARG(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= (xmode == 2 ? 2l * K : (long)K) && ldw >= K,
-                "skinny_gemm: row strides must cover the row and be multiples of 8");
-  VQ3_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)W % 16 == 0) && (!ln_w || (uintptr_t)ln_w % 16 == 0),
-                "skinny_gemm: operands must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  if (M == 1) launch_skinny<1>(xmode, x, W, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else if (M == 2) launch_skinny<2>(xmode, x, W, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else if (M <= 4) launch_skinny<4>(xmode, x, W, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  else launch_skinny<8>(xmode, x, W, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, out_f32, s);
-  VQ3_CHECK_LAUNCH("skinny_gemm");
-  return 0;
-}
-
-extern "C" int vq3_skinny_gemm_fp8(const void* x, const void* Wq, const float* w_scale, void* y, const void* residual,
-                                   const void* ln_w, float eps, int32_t xmode, int32_t M, int32_t N, int32_t K, int64_t ldx,
-                                   int64_t ldw, int64_t ldy, int64_t ldr, void* stream) {
-  VQ3_CHECK_ARG(x && Wq && w_scale && y, "skinny_gemm_fp8: null pointer");
-  VQ3_CHECK_ARG(M >= 1 && M <= 2, "skinny_gemm_fp8: M must be 1 or 2, got %d (prefill / larger batches use vq3_gemm_fp8_nt)", M);
-  VQ3_CHECK_ARG(N > 0 && K > 0 && K % 16 == 0 && K <= 12288, "skinny_gemm_fp8: need K %% 16 == 0 and K <= 12288 (N=%d K=%d)", N, K);
-  VQ3_CHECK_ARG(xmode >= 0 && xmode <= 2 && (xmode != 1 || ln_w), "skinny_gemm_fp8: xmode must be 0, 1 (needs ln_w) or 2");
-  VQ3_CHECK_ARG(ldx % 8 == 0 && ldw % 16 == 0 && ldx >= (xmode == 2 ? 2l * K : (long)K) && ldw >= K,
-                "skinny_gemm_fp8: row strides must cover the row (x: multiple of 8, W: multiple of 16)");
-  VQ3_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)Wq % 16 == 0) && (!ln_w || (uintptr_t)ln_w % 16 == 0),
-                "skinny_gemm_fp8: operands must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int chunks = (K + 1023) / 1024;
-#define VQ3_GO(MT)                                                                                                                  \
-  do {                                                                                                                              \
-    if (chunks <= 3) launch_fp8_skinny<MT, 1>(xmode, x, Wq, w_scale, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, s);       \
-    else if (chunks <= 6) launch_fp8_skinny<MT, 2>(xmode, x, Wq, w_scale, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, s);  \
-    else launch_fp8_skinny<MT, 4>(xmode, x, Wq, w_scale, y, residual, ln_w, eps, M, N, K, ldx, ldw, ldy, ldr, s);                   \
-  } while (0)
-  if (M == 1) VQ3_GO(1);
-  else VQ3_GO(2);
-#undef VQ3_GO
-  VQ3_CHECK_LAUNCH("skinny_gemm_fp8");
-  return 0;
-}
 
 extern "C" int vq3_qwen_decode_qkprep(const void* qkv, const void* q_w, const void* k_w, const void* cos, const void* sin,
                                       const int32_t* lens, void* Q, void* Kcache, void* Vcache, int32_t B, int32_t Hq,
