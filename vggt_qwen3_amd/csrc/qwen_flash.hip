@@ -3,7 +3,7 @@
 // At Stage-1 lengths (L = 200) attention is < 1 % of the FLOPs but was 7 launches and ~270 MB of score traffic per
 // layer; here scores never leave registers.
 //
-// MFMA 32x32x16 bf16 throughout, one wave per 32-row block, no LDS in the main loops:
+// MFMA 32x32x16 bf16 throughout, one wave per 32-row block, no LDS in the forward / dQ main loops:
 //   forward / dQ kernels: S^T = K Q^T (key rows, query columns): the C layout puts the QUERY on the lane, so the online
 //     softmax state, LSE and delta are per-lane scalars, and P^T / dS^T feed the next MFMA straight from the accumulator
 //     registers (k order permuted: element j of lane half h is key 16s + 8(j>>2) + 4h + (j&3)).
@@ -13,7 +13,6 @@
 // d-block db stands for feature d = 4 r + db, so one 8-byte load per key/query row feeds all four d-blocks.
 // Layouts: Q, dQ [B, Hq, L, 128]; K, V, dK, dV [B, Hkv, L, 128]; O, dO token-major rows (b*L + q) with row stride ld,
 // head h at column h*128; LSE (log2 domain, scaled) and Delta f32 [B, Hq, L].
-#include <cstdlib>
 #include "common.h"
 #include "vq3_hip.h"
 
@@ -57,13 +56,6 @@ __device__ __forceinline__ void rows_load(const bf16_t* base, long rowstride, in
 #pragma unroll
   for (int t = 0; t < 8; ++t) f[t] = ld8(p + 16 * t);
 }
-// lanes 0..31 (and their mirrors 32..63) vote on "key kb*32 + r is a real, attended key"
-__device__ __forceinline__ unsigned key_bits(const uint8_t* km, int kb, int r, int L) {
-  const int key = kb * 32 + r;
-  const bool ok = key < L && km[key < L ? key : L - 1] != 0;
-  return (unsigned)(__ballot(ok) & 0xffffffffull);
-}
-
 // The attended-key bits of every tile a wave will walk, computed ONCE into the wave's own LDS words (a keymask byte load inside
 // the tile loop is a dependent global load, and its s_waitcnt vmcnt(0) sits on the tile's critical path). 256 keys = 8 tiles per
 // round trip: four independent byte loads per lane.
@@ -112,9 +104,10 @@ __device__ __forceinline__ unsigned touch_tile(const bf16_t* base, long rowstrid
   return *reinterpret_cast<const unsigned*>(base + (long)row * rowstride + (lane & 1) * 64);
 }
 
-// ---- LDS staging helpers (the dK/dV pass's private stages, the fat kernels' K / V slots)
+// ---- LDS staging helpers of the dK/dV pass (each wave's private Q / dO stages)
 constexpr int DKV_TILE = 32 * 256;                       // bytes of a 32-row x 128-feature bf16 tile
 constexpr int DKV_STAGE = 2 * DKV_TILE + 256;            // Q | dO | 32 LSE + 32 delta floats
+constexpr int DKV_SMEM = 4 * 2 * DKV_STAGE + 4 * 16 * 64 * 4;      // [4 waves][2 stages], then the reduction's f32 [4][16][64]
 __device__ __forceinline__ void dma_tile(const bf16_t* base, long rowstride, int row0, int maxrow, char* dst, int lane) {
 #pragma unroll
   for (int p = 0; p < 8; ++p) {
@@ -163,15 +156,11 @@ __device__ __forceinline__ void tile_flush(const char* tile, bf16_t* base, long 
 
 // ------------------------------------------------------------------------------------------------ forward
 // grid: B * Hkv * nqb blocks of 4 waves; wave g = query head hk*G + g (G = Hq / Hkv <= 4; spare waves idle)
-// One 32-row query block of one query head: the wave's whole forward. LDS_KV = false: K / V tiles come from global memory (rows +
-// 8-byte gathers, all loads of a tile issued before its first use); true: they sit in LDS slots (slot li = the li-th attended tile of
-// the sample: [K tile | V tile], 16-byte chunks XOR (row & 15), staged by dma_tile) and a step has no global load at all. Same
-// arithmetic in the same order either way.
-template <bool LDS_KV>
+// One 32-row query block of one query head: the wave's whole forward. K / V tiles come from global memory (rows + 8-byte gathers).
 __device__ __forceinline__ void fwd_block(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                           bf16_t* __restrict__ O, float* __restrict__ LSE, int L, int Hq, int Hkv, long ldo, float scale,
                                           int b, int hk, int hq, int qb, const unsigned* bits_g, const unsigned* list_g, int nlist,
-                                          const char* slots, char* otile, const bf16x8* qpre = nullptr) {
+                                          char* otile) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 31, h = lane >> 5;
   const int q = qb * 32 + r, qc = q < L ? q : L - 1;
@@ -180,7 +169,7 @@ __device__ __forceinline__ void fwd_block(const bf16_t* __restrict__ Q, const bf
   const bf16_t* Vb = V + ((long)b * Hkv + hk) * L * D;
   bf16x8 qf[8];
 #pragma unroll
-  for (int s = 0; s < 8; ++s) qf[s] = qpre ? qpre[s] : ld8(Qr + 16 * s);      // (qpre: the caller requested the rows a query block ahead)
+  for (int s = 0; s < 8; ++s) qf[s] = ld8(Qr + 16 * s);
   f32x16 o[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db)
@@ -192,19 +181,12 @@ __device__ __forceinline__ void fwd_block(const bf16_t* __restrict__ Q, const bf
     const int kb = (int)list_g[li];
     // every load of the tile is issued before its first use: one memory round trip per tile; the next attended tile is touched
     // into L2 meanwhile
-    unsigned tk = 0, tv = 0;
     bf16x8 kc[8];
     u32x2 vc[2][8];
-    const char* slot = slots + li * (2 * 32 * 256);
-    if (LDS_KV) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) kc[t] = *reinterpret_cast<const bf16x8*>(slot + r * 256 + (((2 * t + h) ^ (r & 15)) << 4));
-    } else {
-      const int nkb = (int)list_g[li + 1 < nlist ? li + 1 : li];
-      tk = touch_tile(Kb, D, nkb * 32, L - 1); tv = touch_tile(Vb, D, nkb * 32, L - 1);
-      rows_load(Kb, D, kb * 32 + r, h, L - 1, kc);
-      gather_load(Vb, D, kb * 32, h, r, L - 1, vc);
-    }
+    const int nkb = (int)list_g[li + 1 < nlist ? li + 1 : li];
+    const unsigned tk = touch_tile(Kb, D, nkb * 32, L - 1), tv = touch_tile(Vb, D, nkb * 32, L - 1);
+    rows_load(Kb, D, kb * 32 + r, h, L - 1, kc);
+    gather_load(Vb, D, kb * 32, h, r, L - 1, vc);
     f32x16 s;
 #pragma unroll
     for (int i = 0; i < 16; ++i) s[i] = 0.f;
@@ -239,13 +221,12 @@ __device__ __forceinline__ void fwd_block(const bf16_t* __restrict__ Q, const bf
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp) {
       bf16x8 vf[4];
-      if (LDS_KV) lds_gather(slot + 32 * 256, sp, h, r, vf);
-      else gather_split(vc[sp], vf);
+      gather_split(vc[sp], vf);
       const bf16x8 pf = pack8(s, sp);
 #pragma unroll
       for (int db = 0; db < 4; ++db) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[db], pf, o[db], 0, 0, 0);
     }
-    if (!LDS_KV) asm volatile("" ::"v"(tk), "v"(tv));   // keeps the touch loads alive; their wait lands here, after the tile's MFMAs
+    asm volatile("" ::"v"(tk), "v"(tv));   // keeps the touch loads alive; their wait lands here, after the tile's MFMAs
   }
   const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
@@ -278,18 +259,16 @@ __global__ __launch_bounds__(256) void qwen_flash_fwd_kernel(const bf16_t* __res
   if (g >= G) return;
   key_bits_all(keymask + (long)b * L, qb + 1, L, sbits[g]);
   const int nlist = compact_tiles(sbits[g], qb + 1, slist[g]);
-  fwd_block<false>(Q, K, V, O, LSE, L, Hq, Hkv, ldo, scale, b, hk, hq, qb, sbits[g], slist[g], nlist, nullptr, ostage[g]);
+  fwd_block(Q, K, V, O, LSE, L, Hq, Hkv, ldo, scale, b, hk, hq, qb, sbits[g], slist[g], nlist, ostage[g]);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dQ (+ delta)
-// One 32-row query block of one query head in the dQ pass (LDS_KV as in fwd_block: K / V tiles from global memory or from the
-// workgroup's LDS slots; same arithmetic either way).
-template <bool LDS_KV>
+// One 32-row query block of one query head in the dQ pass (K / V tiles from global memory, as in fwd_block); also writes delta.
 __device__ __forceinline__ void dq_block(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                          const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
                                          float* __restrict__ Delta, bf16_t* __restrict__ dQ, int L, int Hq, int Hkv, long ldo, long lddo,
                                          float scale, int b, int hk, int hq, int qb, const unsigned* bits_g, const unsigned* list_g,
-                                         int nlist, const char* slots, char* otile) {
+                                         int nlist, char* otile) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 31, h = lane >> 5;
   const int q = qb * 32 + r, qc = q < L ? q : L - 1;
@@ -318,23 +297,13 @@ __device__ __forceinline__ void dq_block(const bf16_t* __restrict__ Q, const bf1
   const float sl2e = scale * LOG2E;
   for (int li = 0; li < nlist; ++li) {
     const int kb = (int)list_g[li];
-    unsigned tk = 0, tv = 0;
     bf16x8 kc[8], vc[8];
     u32x2 gc[2][8];
-    const char* slot = slots + li * (2 * 32 * 256);
-    if (LDS_KV) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        kc[t] = *reinterpret_cast<const bf16x8*>(slot + r * 256 + (((2 * t + h) ^ (r & 15)) << 4));
-        vc[t] = *reinterpret_cast<const bf16x8*>(slot + 32 * 256 + r * 256 + (((2 * t + h) ^ (r & 15)) << 4));
-      }
-    } else {
-      const int nkb = (int)list_g[li + 1 < nlist ? li + 1 : li];
-      tk = touch_tile(Kb, D, nkb * 32, L - 1); tv = touch_tile(Vb, D, nkb * 32, L - 1);
-      rows_load(Kb, D, kb * 32 + r, h, L - 1, kc);
-      rows_load(Vb, D, kb * 32 + r, h, L - 1, vc);
-      gather_load(Kb, D, kb * 32, h, r, L - 1, gc);
-    }
+    const int nkb = (int)list_g[li + 1 < nlist ? li + 1 : li];
+    const unsigned tk = touch_tile(Kb, D, nkb * 32, L - 1), tv = touch_tile(Vb, D, nkb * 32, L - 1);
+    rows_load(Kb, D, kb * 32 + r, h, L - 1, kc);
+    rows_load(Vb, D, kb * 32 + r, h, L - 1, vc);
+    gather_load(Kb, D, kb * 32, h, r, L - 1, gc);
     f32x16 s, dp;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -354,13 +323,12 @@ __device__ __forceinline__ void dq_block(const bf16_t* __restrict__ Q, const bf1
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp) {
       bf16x8 kf[4];
-      if (LDS_KV) lds_gather(slot, sp, h, r, kf);
-      else gather_split(gc[sp], kf);
+      gather_split(gc[sp], kf);
       const bf16x8 dsf = pack8(s, sp);
 #pragma unroll
       for (int db = 0; db < 4; ++db) dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[db], dsf, dq[db], 0, 0, 0);
     }
-    if (!LDS_KV) asm volatile("" ::"v"(tk), "v"(tv));
+    asm volatile("" ::"v"(tk), "v"(tv));
   }
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -391,18 +359,24 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dq_kernel(const bf16_t* __
   if (g >= G) return;
   key_bits_all(keymask + (long)b * L, qb + 1, L, sbits[g]);
   const int nlist = compact_tiles(sbits[g], qb + 1, slist[g]);
-  dq_block<false>(Q, K, V, O, dO, LSE, Delta, dQ, L, Hq, Hkv, ldo, lddo, scale, b, hk, hq, qb, sbits[g], slist[g], nlist, nullptr, ostage[g]);
+  dq_block(Q, K, V, O, dO, LSE, Delta, dQ, L, Hq, Hkv, ldo, lddo, scale, b, hk, hq, qb, sbits[g], slist[g], nlist, ostage[g]);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
-// grid: B * Hkv * nkb blocks; wave g = query head of the group; the four waves' accumulators meet in LDS.
-__global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                                const bf16_t* __restrict__ V, const uint8_t* __restrict__ keymask,
-                                                                const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
-                                                                const float* __restrict__ Delta, bf16_t* __restrict__ dK,
-                                                                bf16_t* __restrict__ dV, int L, int Hq, int Hkv, long lddo,
-                                                                float scale, int S, long part_stride) {
-  __shared__ float red[4][16][64];     // one f32x16 accumulator block per wave
+// grid: B * Hkv * nkb * S blocks; wave g = query head of the group; the four waves' accumulators meet in LDS.
+// The kernel runs one wave per SIMD (the accumulators for dK^T and dV^T alone are 128 registers), so nothing could hide the round trip
+// of a q-block's ~56 global loads per lane (rows of Q and dO, their 8-byte "transposed" gathers, LSE, delta): read straight into
+// registers a step cost ~4 us for 0.5 us of MFMA work. So each wave owns two LDS stages of {Q tile, dO tile, LSE | delta} (32 rows x
+// 256 B each, 16-byte chunks XOR (row & 15)) filled by global_load_lds one q-block AHEAD (17 DMA instructions per stage, counted vmcnt -
+// no barrier: a wave reads only what it staged itself), and both operand forms are LDS reads: the rows as ds_read_b128, the gathers
+// as ds_read_b64 of the same tile.
+__global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_lds_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+                                                                    const bf16_t* __restrict__ V, const uint8_t* __restrict__ keymask,
+                                                                    const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
+                                                                    const float* __restrict__ Delta, bf16_t* __restrict__ dK,
+                                                                    bf16_t* __restrict__ dV, int L, int Hq, int Hkv, long lddo,
+                                                                    float scale, int S, long part_stride) {
+  extern __shared__ __attribute__((aligned(16))) char dkv_smem[];      // [4 waves][2 stages][DKV_STAGE], then red
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int nkb = (L + 31) / 32;
@@ -424,144 +398,6 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_kernel(const bf16_t* _
   const bool key_ok = key < L && keymask[(long)b * L + kc] != 0;
   if (__ballot(key_ok) == 0ull) {
     // no attended key in this tile (padding): dK = dV = 0 exactly, for every head of the group - same answer in all four waves
-    if (key < L && g == 0) {
-      bf16_t* dKz = dK + (((long)b * Hkv + hk) * L + key) * D + 64 * h;
-      bf16_t* dVz = dV + (((long)b * Hkv + hk) * L + key) * D + 64 * h;
-      const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        *reinterpret_cast<u32x4*>(dKz + 8 * c) = z;
-        *reinterpret_cast<u32x4*>(dVz + 8 * c) = z;
-      }
-    }
-    return;
-  }
-  bf16x8 kf[8], vf[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) { kf[s] = ld8(Kr + 16 * s); vf[s] = ld8(Vr + 16 * s); }
-  f32x16 dk[4], dv[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dk[db][i] = 0.f; dv[db][i] = 0.f; }
-  const float sl2e = scale * LOG2E;
-  if (active) {
-    const bf16_t* Qh = Q + ((long)b * Hq + hq) * L * D;
-    const bf16_t* dOh = dO + (long)b * L * lddo + (long)hq * D;
-    const float* lse_h = LSE + ((long)b * Hq + hq) * L;
-    const float* del_h = Delta + ((long)b * Hq + hq) * L;
-    for (int qb = kb + sp; qb < nkb; qb += S) {
-      // every load of the tile is issued before its first use: one memory round trip per tile instead of four; the next
-      // q-block's Q and dO tiles are touched into L2 meanwhile
-      const int nq = qb + S < nkb ? qb + S : qb;
-      const unsigned tq = touch_tile(Qh, D, nq * 32, L - 1), tdo = touch_tile(dOh, lddo, nq * 32, L - 1);
-      bf16x8 qrow[8], dorow[8];
-      u32x2 gdo[2][8], gq[2][8];
-      f32x4 lse4[4], del4[4];
-      rows_load(Qh, D, qb * 32 + r, h, L - 1, qrow);
-      rows_load(dOh, lddo, qb * 32 + r, h, L - 1, dorow);
-      gather_load(dOh, lddo, qb * 32, h, r, L - 1, gdo);                 // dO^T rows d = 4r + db
-      gather_load(Qh, D, qb * 32, h, r, L - 1, gq);                       // Q^T rows
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {      // rows rho(4c .. 4c+3, h) = 8c + 4h .. +3 are consecutive
-        // unconditional 16-byte loads (a branch here would drain the load queue): a group that starts past the end is
-        // clamped (all its rows are masked), a group that straddles the end reads into the next row / the 4-float slack
-        // the caller guarantees behind LSE and Delta - those rows are masked too
-        int q0 = qb * 32 + 8 * c + 4 * h;
-        q0 = q0 < L ? q0 : (L >= 4 ? L - 4 : 0);
-        lse4[c] = *reinterpret_cast<const f32x4*>(lse_h + q0);
-        del4[c] = *reinterpret_cast<const f32x4*>(del_h + q0);
-      }
-      f32x16 s, dp;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qrow[t], kf[t], s, 0, 0, 0);      // S[q, key]
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dorow[t], vf[t], dp, 0, 0, 0);   // dP[q, key]
-      }
-      f32x16 p;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int qg = qb * 32 + rho(i, h);
-        const bool ok = key_ok && qg < L && key <= qg;
-        const float pv = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], sl2e, -lse4[i >> 2][i & 3])) : 0.f;
-        p[i] = pv;
-        // selected, not just multiplied by pv = 0: a group that straddles L reads delta from the caller's slack, whatever it holds
-        s[i] = ok ? pv * (dp[i] - del4[i >> 2][i & 3]) * scale : 0.f;     // dS[q, key]
-      }
-#pragma unroll
-      for (int sp = 0; sp < 2; ++sp) {
-        bf16x8 a[4];
-        gather_split(gdo[sp], a);
-        const bf16x8 pf = pack8(p, sp);
-#pragma unroll
-        for (int db = 0; db < 4; ++db) dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[db], pf, dv[db], 0, 0, 0);
-        gather_split(gq[sp], a);
-        const bf16x8 dsf = pack8(s, sp);
-#pragma unroll
-        for (int db = 0; db < 4; ++db) dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[db], dsf, dk[db], 0, 0, 0);
-      }
-      asm volatile("" ::"v"(tq), "v"(tdo));
-    }
-  }
-  // sum the G query heads: 8 accumulator blocks (dk[0..3], dv[0..3]), each reduced through LDS; wave (blk & 3) keeps blk
-  bf16_t* dKr = dK + (((long)b * Hkv + hk) * L + kc) * D;
-  bf16_t* dVr = dV + (((long)b * Hkv + hk) * L + kc) * D;
-  f32x16 keep[2];
-#pragma unroll
-  for (int blk = 0; blk < 8; ++blk) {
-    const f32x16& mine = blk < 4 ? dk[blk] : dv[blk - 4];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) red[g][i][lane] = mine[i];
-    __syncthreads();
-    if ((blk & 3) == g) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) keep[blk >> 2][i] = red[0][i][lane] + red[1][i][lane] + red[2][i][lane] + red[3][i][lane];
-    }
-  }
-  if (key >= L) return;
-  // wave g holds d-block db = g of both dK^T and dV^T: element i is feature d = 4 rho(i) + g
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    dKr[4 * rho(i, h) + g] = f2bf(keep[0][i]);
-    dVr[4 * rho(i, h) + g] = f2bf(keep[1][i]);
-  }
-}
-
-
-// ------------------------------------------------------------------------------------------------ backward: dK, dV with LDS-staged Q / dO
-// Same mapping and arithmetic as qwen_flash_bwd_dkv_kernel; what changes is where a q-block's operands come from. There every step
-// began with ~56 global loads per lane (rows of Q and dO, their 8-byte "transposed" gathers, LSE, delta) whose round trip nothing could
-// hide: the kernel runs one wave per SIMD (accumulators for dK^T and dV^T alone are 128 registers), so a step cost ~4 us for 0.5 us of
-// MFMA work. Here each wave owns two LDS stages of {Q tile, dO tile, LSE | delta} (32 rows x 256 B each, 16-byte chunks XOR (row & 15))
-// filled by global_load_lds one q-block AHEAD (17 DMA instructions per stage, counted vmcnt - no barrier: a wave reads only what it
-// staged itself), and both operand forms are LDS reads: the rows as ds_read_b128, the gathers as ds_read_b64 of the same tile.
-__global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_lds_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                                    const bf16_t* __restrict__ V, const uint8_t* __restrict__ keymask,
-                                                                    const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
-                                                                    const float* __restrict__ Delta, bf16_t* __restrict__ dK,
-                                                                    bf16_t* __restrict__ dV, int L, int Hq, int Hkv, long lddo,
-                                                                    float scale, int S, long part_stride) {
-  extern __shared__ __attribute__((aligned(16))) char dkv_smem[];      // [4 waves][2 stages][DKV_STAGE], then red
-  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int nkb = (L + 31) / 32;
-  const int sp = blockIdx.x % S;
-  const int bid = blockIdx.x / S;
-  const int nbh = (gridDim.x / S) / nkb;
-  const int kb = bid / nbh;                                     // kb = 0 walks the most q-blocks: heaviest first
-  dK += sp * part_stride;
-  dV += sp * part_stride;
-  const int hk = (bid % nbh) % Hkv, b = (bid % nbh) / Hkv;
-  const int G = Hq / Hkv, hq = hk * G + g;
-  const bool active = g < G;
-  const int key = kb * 32 + r, kc = key < L ? key : L - 1;
-  const bf16_t* Kr = K + (((long)b * Hkv + hk) * L + kc) * D + 8 * h;
-  const bf16_t* Vr = V + (((long)b * Hkv + hk) * L + kc) * D + 8 * h;
-  const bool key_ok = key < L && keymask[(long)b * L + kc] != 0;
-  if (__ballot(key_ok) == 0ull) {
     if (key < L && g == 0) {
       bf16_t* dKz = dK + (((long)b * Hkv + hk) * L + key) * D + 64 * h;
       bf16_t* dVz = dV + (((long)b * Hkv + hk) * L + key) * D + 64 * h;
@@ -653,10 +489,9 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_lds_kernel(const bf16_
       stage ^= 1;
     }
   }
-  // sum the G query heads (as in qwen_flash_bwd_dkv_kernel); the reduction scratch sits behind the stages
+  // sum the G query heads: 8 accumulator blocks (dk[0..3], dv[0..3]), each reduced through LDS; wave (blk & 3) keeps blk. The
+  // reduction scratch sits behind the stages
   float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(dkv_smem + 4 * 2 * DKV_STAGE);
-  bf16_t* dKr = dK + (((long)b * Hkv + hk) * L + kc) * D;
-  bf16_t* dVr = dV + (((long)b * Hkv + hk) * L + kc) * D;
   f32x16 keep[2];
 #pragma unroll
   for (int blk = 0; blk < 8; ++blk) {
@@ -672,7 +507,6 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_lds_kernel(const bf16_
   }
   // wave g holds feature d = 4 rho(i) + g of both tiles: 2-byte pieces 8 bytes apart. Through two LDS tiles (the stages are dead: every
   // wave passed the reduction's barriers) they leave as whole 256-byte rows, 16 B per thread
-  (void)dKr; (void)dVr;
   char* const tk = dkv_smem;
   char* const tv = dkv_smem + DKV_TILE;
 #pragma unroll
@@ -695,7 +529,6 @@ __global__ __launch_bounds__(256) void qwen_flash_bwd_dkv_lds_kernel(const bf16_
     }
   }
 }
-constexpr int DKV_SMEM = 4 * 2 * DKV_STAGE + 4 * 16 * 64 * 4;
 
 }  // namespace
 
@@ -721,9 +554,6 @@ extern "C" int vq3_qwen_flash_fwd(const void* Q, const void* K, const void* V, c
   return 0;
 }
 
-static int launch_dkv(const void* Q, const void* K, const void* V, const void* keymask, const void* dO, const float* LSE, float* Delta,
-                      void* dK, void* dV, int kv_parts, int B, int L, int Hq, int Hkv, long lddo, float scale, hipStream_t s);
-
 extern "C" int vq3_qwen_flash_bwd(const void* Q, const void* K, const void* V, const void* keymask, const void* O,
                                   const void* dO, const float* LSE, float* Delta, void* dQ, void* dK, void* dV, int32_t kv_parts,
                                   int32_t B, int32_t L, int32_t Hq, int32_t Hkv, int32_t Dh, int64_t ldo, int64_t lddo,
@@ -732,38 +562,19 @@ extern "C" int vq3_qwen_flash_bwd(const void* Q, const void* K, const void* V, c
   if (flash_check("qwen_flash_bwd", B, L, Hq, Hkv, Dh)) return 1;
   VQ3_CHECK_ARG(ldo >= (long)Hq * D && lddo >= (long)Hq * D && ldo % 8 == 0 && lddo % 8 == 0, "qwen_flash_bwd: bad row strides");
   VQ3_CHECK_ARG(kv_parts >= 1 && kv_parts <= 4, "qwen_flash_bwd: kv_parts must be 1..4");
+  // the dK/dV kernel's stages are more than the 64 KiB a kernel gets without asking (gfx950 has 160 KiB per workgroup)
+  static const bool dkv_lds = hipFuncSetAttribute((const void*)qwen_flash_bwd_dkv_lds_kernel,
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, DKV_SMEM) == hipSuccess;
+  if (!dkv_lds) (void)hipGetLastError();      // reported here, not by a later launch check
+  VQ3_CHECK_ARG(dkv_lds, "qwen_flash_bwd: the device refuses the dK/dV kernel's %d bytes of dynamic LDS", DKV_SMEM);
   const int nqb = (L + 31) / 32;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(qwen_flash_bwd_dq_kernel, dim3(B * Hkv * nqb), dim3(256), 0, s, (const bf16_t*)Q, (const bf16_t*)K,
                      (const bf16_t*)V, (const uint8_t*)keymask, (const bf16_t*)O, (const bf16_t*)dO, LSE, Delta, (bf16_t*)dQ, L,
                      Hq, Hkv, (long)ldo, (long)lddo, scale);
-  const int rc_dkv = launch_dkv(Q, K, V, keymask, dO, LSE, Delta, dK, dV, kv_parts, B, L, Hq, Hkv, (long)lddo, scale, s);
-  if (rc_dkv) return rc_dkv;
+  hipLaunchKernelGGL(qwen_flash_bwd_dkv_lds_kernel, dim3(B * Hkv * nqb * kv_parts), dim3(256), DKV_SMEM, s, (const bf16_t*)Q,
+                     (const bf16_t*)K, (const bf16_t*)V, (const uint8_t*)keymask, (const bf16_t*)dO, LSE, Delta, (bf16_t*)dK,
+                     (bf16_t*)dV, L, Hq, Hkv, (long)lddo, scale, (int)kv_parts, (long)B * Hkv * L * D);
   VQ3_CHECK_LAUNCH("qwen_flash_bwd");
-  return 0;
-}
-
-static int launch_dkv(const void* Q, const void* K, const void* V, const void* keymask, const void* dO, const float* LSE, float* Delta,
-                      void* dK, void* dV, int kv_parts, int B, int L, int Hq, int Hkv, long lddo, float scale, hipStream_t s) {
-  const int nqb = (L + 31) / 32;
-  // dK / dV pass: the LDS-staged kernel (operands of the next q-block in flight while this one multiplies); VQ3_QWEN_DKV_LDS=0 = the
-  // register-staged one
-  static int dkv_lds = -1;
-  if (dkv_lds < 0) {
-    const char* e = getenv("VQ3_QWEN_DKV_LDS");
-    dkv_lds = e ? atoi(e) : 1;
-    if (dkv_lds && hipFuncSetAttribute((const void*)qwen_flash_bwd_dkv_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_SMEM) != hipSuccess) {
-      (void)hipGetLastError();
-      dkv_lds = 0;
-    }
-  }
-  if (dkv_lds)
-    hipLaunchKernelGGL(qwen_flash_bwd_dkv_lds_kernel, dim3(B * Hkv * nqb * kv_parts), dim3(256), DKV_SMEM, s, (const bf16_t*)Q,
-                       (const bf16_t*)K, (const bf16_t*)V, (const uint8_t*)keymask, (const bf16_t*)dO, LSE, Delta, (bf16_t*)dK,
-                       (bf16_t*)dV, L, Hq, Hkv, (long)lddo, scale, (int)kv_parts, (long)B * Hkv * L * D);
-  else
-    hipLaunchKernelGGL(qwen_flash_bwd_dkv_kernel, dim3(B * Hkv * nqb * kv_parts), dim3(256), 0, s, (const bf16_t*)Q, (const bf16_t*)K,
-                       (const bf16_t*)V, (const uint8_t*)keymask, (const bf16_t*)dO, LSE, Delta, (bf16_t*)dK, (bf16_t*)dV, L, Hq,
-                       Hkv, (long)lddo, scale, (int)kv_parts, (long)B * Hkv * L * D);
   return 0;
 }

@@ -949,7 +949,7 @@ def qwen_flash_fwd(Q, K, V, keymask, B, L, Hq, Hkv, D, scale, out: Optional[torc
     _req(keymask, torch.uint8, "qwen_flash keymask")
     assert Q.shape == (B, Hq, L, D) and K.shape == (B, Hkv, L, D) and V.shape == K.shape and keymask.shape == (B, L)
     O = _out2d(out, B * L, Hq * D, Q, "qwen_flash_fwd")
-    lse = torch.empty(B * Hq * L + 4, device=Q.device, dtype=F32)[: B * Hq * L].view(B, Hq, L)   # 16 B of slack
+    lse = torch.empty((B, Hq, L), device=Q.device, dtype=F32)
     check(_lib.load().vq3_qwen_flash_fwd(Q.data_ptr(), K.data_ptr(), V.data_ptr(), keymask.data_ptr(), O.data_ptr(),
                                          lse.data_ptr(), B, L, Hq, Hkv, D, Hq * D, scale, _stream()),
           "vq3_qwen_flash_fwd")
@@ -958,7 +958,7 @@ def qwen_flash_fwd(Q, K, V, keymask, B, L, Hq, Hkv, D, scale, out: Optional[torc
 
 def qwen_flash_bwd(Q, K, V, keymask, O, dO, lse, B, L, Hq, Hkv, D, scale, kv_parts: Optional[int] = None):
     """O, dO: bf16 [B*L, Hq*D] token-major. -> dQ [B,Hq,L,D]; dK, dV bf16 [kv_parts, B,Hkv,L,D] partial slabs (kv_parts = 1 gives
-    plain [B,Hkv,L,D], the default); qwen_qkprep_bwd adds the slabs. Worth it when most key tiles are padding (Qwen3ForCausalLM.forward_hidden decides)."""
+    plain [B,Hkv,L,D], the default); qwen_qkprep_bwd adds the slabs. The model runs kv_parts = 1 (DESIGN_HISTORY.md §9)."""
     _req(O, BF16, "flash_bwd O"); _req(dO, BF16, "flash_bwd dO"); _req(lse, F32, "flash_bwd lse")
     assert O.shape == (B * L, Hq * D) and dO.shape == O.shape and O.stride(1) == 1 and dO.stride(1) == 1
     dev = Q.device
@@ -968,7 +968,7 @@ def qwen_flash_bwd(Q, K, V, keymask, O, dO, lse, B, L, Hq, Hkv, D, scale, kv_par
     kv_shape = (B, Hkv, L, D) if kv_parts == 1 else (kv_parts, B, Hkv, L, D)
     dK = torch.empty(kv_shape, device=dev, dtype=BF16)
     dV = torch.empty(kv_shape, device=dev, dtype=BF16)
-    delta = torch.empty(B * Hq * L + 4, device=dev, dtype=F32)
+    delta = torch.empty(B * Hq * L, device=dev, dtype=F32)
     check(_lib.load().vq3_qwen_flash_bwd(Q.data_ptr(), K.data_ptr(), V.data_ptr(), keymask.data_ptr(), O.data_ptr(),
                                          dO.data_ptr(), lse.data_ptr(), delta.data_ptr(), dQ.data_ptr(), dK.data_ptr(),
                                          dV.data_ptr(), kv_parts, B, L, Hq, Hkv, D, O.stride(0), dO.stride(0), scale,

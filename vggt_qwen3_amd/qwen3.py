@@ -508,7 +508,7 @@ class Qwen3ForCausalLM(nn.Module):
             ctx.update(qkv=qkv, Q=Q, K=K, V=V, qr=qr, kr=kr, P=P, ao=ao)
         return ao
 
-    def forward_hidden(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, save: bool, plan_key=None):
+    def forward_hidden(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, save: bool):
         """36x decoder layer (modeling_qwen3.py:294-323, 367-427). Returns (h_last [B*L,H] pre-final-norm, saved)."""
         B, L0, H = inputs_embeds.shape
         c = self.config
@@ -518,23 +518,9 @@ class Qwen3ForCausalLM(nn.Module):
             inputs_embeds = torch.cat([inputs_embeds, inputs_embeds.new_zeros((B, L - L0, H))], dim=1)
             attention_mask = torch.cat([attention_mask, attention_mask.new_zeros((B, L - L0))], dim=1)
         keymask = (attention_mask != 0).to(torch.uint8).contiguous()
-        kv_parts = 1
-        dkv_lds = os.environ.get("VQ3_QWEN_DKV_LDS", "1") != "0"
-        if "VQ3_QWEN_KV_PARTS" in os.environ:
-            kv_parts = int(os.environ["VQ3_QWEN_KV_PARTS"])
-        elif save and self._flash and L >= 128 and not dkv_lds:
-            # The dK/dV pass walks, per 32-key tile, every query block behind it - its longest serial chain. Key tiles without an
-            # attended key leave at once, so when most of a padded batch's tiles are empty there are CUs to spare and two
-            # workgroups share each live tile's walk (partial slabs, summed by the q/k-prep backward); with dense masks every
-            # workgroup is live and splitting would only add rounds. One tiny host read per forward decides.
-            nkb = (L + 31) // 32
-            pad = nkb * 32 - L
-            km = torch.nn.functional.pad(keymask, (0, pad)) if pad else keymask
-            count = lambda: int(km.view(B, nkb, 32).any(-1).sum().item())
-            live = PLAN.get(("live_key_tiles", L), plan_key, count) if plan_key is not None else count()
-            kv_parts = 2 if live * 2 <= B * nkb else 1
-        # (round 3: with the LDS-staged dK/dV kernel - the default - a q-block step costs ~1 us instead of ~4, a workgroup's fixed cost
-        # dominates and ONE workgroup per live key tile wins (133.7 against 132.4 samples/s): no split, and no host read to decide it)
+        # dK/dV pass: one workgroup per live key tile. A q-block step costs ~1 us, so a workgroup's fixed cost dominates and sharing a
+        # tile's walk loses (133.7 against 132.4 samples/s, DESIGN_HISTORY.md §9); the override is the model's only way to the split
+        kv_parts = int(os.environ.get("VQ3_QWEN_KV_PARTS", "1"))
         h = inputs_embeds.reshape(B * L, H)
         saved: List[dict] = []
         if self.lora_frozen:

@@ -547,7 +547,7 @@ class VGGTQwen3VLM(nn.Module):
                                       guard=lambda: ((tm._fp8.get("l0.qkv", (None,))[0],) if getattr(tm, "_fp8", None) else ()))
             saved = {"layers": [], "B": B, "L": Lp_, "L0": L}
         else:
-            h_last, saved = tm.forward_hidden(emb, attention_mask, save=need_grad, plan_key=(attention_mask0,))
+            h_last, saved = tm.forward_hidden(emb, attention_mask, save=need_grad)
         loss, head_ctx = tm.loss_head(h_last, labels, save=need_grad, L=saved["L"], plan_key=(labels0,), groups=loss_groups)
         live = None
         if need_grad:
