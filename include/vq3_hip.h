@@ -416,6 +416,28 @@ int vq3_greedy_pick(const void* logits_bf16, int64_t ld_logits, float* work, int
                     void* stream);
 /* lens[b] += 1 for b < B (B <= 64), *step += 1 (either pointer may be NULL): the last launch of a decode step. */
 int vq3_decode_advance(int32_t* lens, int32_t B, int32_t* step, void* stream);
+/* Per-token log-probabilities of bf16 logits [n, ld] with V valid columns (replaces transformers `output_logits` / the forward's
+ * `logits` followed by log_softmax + gather): for row i with target t = targets[i], in f32, lse[i] = logsumexp(logits[i, :V]),
+ * logprob[i] = logits[i, t] - lse[i], and rank[i] (i32) = the number of columns that beat the target (greater, or equal and left of
+ * it): 0 exactly where vq3_greedy_pick's first-index argmax picks t. A target outside [0, V) (-100) reads nothing: logprob 0, rank -1,
+ * lse still written. lse / rank may be NULL. Read-only: the logits are never written, columns [V, ld) never read into a result; one
+ * pass over the rows, no atomics (the same bits run after run). slices: 1 = one workgroup per row, 2..64 = the vocabulary of each row
+ * split over that many workgroups plus a fixed-order combine (few rows), 0 = chosen from n. Different values of slices sum in different
+ * orders (last-bit differences in lse / logprob): a caller whose results must not depend on n passes a fixed one. A row that is -inf
+ * throughout gives lse -inf and logprob -inf. work: >= n * 192 four-byte slots, needed unless slices == 1 (NULL allowed then).
+ * n <= 65535. */
+int vq3_token_logprob(const void* logits_bf16, int64_t ld_logits, int32_t n, int32_t V, const int32_t* targets, float* logprob_f32,
+                      float* lse_f32, int32_t* rank_i32, void* work, int32_t slices, void* stream);
+/* The same for one decode step, after vq3_greedy_pick and before vq3_decode_advance (replaces GenerationMixin
+ * compute_transition_scores on `output_logits`: the model's own distribution, before the logits processors): row b's target is
+ * next_ids[b], its result goes to column *step - prompt_offset of logprob_f32 / rank_i32 (NULL allowed), both [B, cols]; a column
+ * outside [0, cols) writes nothing. Every quantity that varies per step is read from device memory, so the call sits in a captured
+ * graph. done: i32 [B], zeroed by the caller before the first step and owned by this call from then on - the finished flags as they
+ * stood BEFORE the pick: a row that was already finished (its pick is a pad) gets exactly 0.0 / -1, the step that emits the eos its
+ * real value, whatever pad_id is. work: >= B * 192 four-byte slots. */
+int vq3_token_logprob_step(const void* logits_bf16, int64_t ld_logits, int32_t B, int32_t V, const int32_t* next_ids,
+                           const int32_t* step, int32_t prompt_offset, const int32_t* finished, int32_t* done, float* logprob_f32,
+                           int32_t* rank_i32, int32_t cols, void* work, void* stream);
 
 /* All decoder layers of one decode step for ONE row (B = 1, the reference's callers) in one persistent launch: per layer
  * q|k|v[+RMSNorm] -> q/k-norm + RoPE + cache append + attention -> o[+residual] -> gate|up[+RMSNorm] + SwiGLU -> down[+residual]

@@ -119,6 +119,8 @@ SIGNATURES = {
     "vq3_qwen_decode_attn": [c_p] * 5 + [i32, i32, i32, i32, i32, f32, c_p],
     "vq3_greedy_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, c_p],
     "vq3_decode_advance": [c_p, i32, c_p, c_p],
+    "vq3_token_logprob": [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p],
+    "vq3_token_logprob_step": [c_p, i64, i32, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p],
     "vq3_qwen_decode_layers_supported": [i32] * 6,
     "vq3_qwen_decode_layers_workspace_bytes": [],
     "vq3_qwen_decode_layers": [C.POINTER(DecodeLayersDesc), c_p],

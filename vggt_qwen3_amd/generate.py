@@ -57,7 +57,7 @@ def _row_spans(attention_mask: torch.Tensor) -> List[Tuple[int, int]]:
 class DecodeState:
     """Device-resident state of one generate() call."""
 
-    def __init__(self, tm, B: int, Lmax: int, gen_cols: int):
+    def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0):
         c, dev = tm.config, tm.flat_w.device
         self.B, self.Lmax = B, Lmax
         nl = c.num_hidden_layers
@@ -69,6 +69,13 @@ class DecodeState:
         self.next_ids = torch.zeros(B, device=dev, dtype=torch.int32)
         self.generated = torch.zeros((B, gen_cols), device=dev, dtype=torch.int64)
         self.work = torch.zeros(B * 128 + 8, device=dev, dtype=F32)     # pick partials + overflow flag
+        # output_logprobs: one f32 per new token, the kernel's own record of the finished flags before each pick, its partials
+        self.logprobs = None
+        if logprob_cols > 0:
+            self.logprobs = torch.zeros((B, logprob_cols), device=dev, dtype=F32)
+            self.prompt_cols = prompt_cols
+            self.lp_done = torch.zeros(B, device=dev, dtype=torch.int32)
+            self.lp_work = torch.zeros(B * ops.LOGPROB_WORK_PER_ROW, device=dev, dtype=F32)
         # B = 1 at Qwen3-4B's shape: all decoder layers of a step in ONE persistent launch (csrc/decode_layers.hip) instead of six
         # launches per layer; every other case decodes with one launch per projection
         self.persistent = None
@@ -111,6 +118,8 @@ def _logits_and_pick(tm, st: DecodeState, h: torch.Tensor, opts) -> None:
     logits = ops.skinny_linear(h, tm._w["embed"], n=tm.vocab, ln_w=tm._w["norm"], eps=c.rms_norm_eps)
     ops.greedy_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
                     opts["pad"], st.next_ids, tm.vocab)
+    if st.logprobs is not None:     # the raw logits' log-probability of the id just picked, into column step - prompt_cols
+        ops.token_logprob_step(logits, tm.vocab, st.next_ids, st.step, st.prompt_cols, st.finished, st.lp_done, st.logprobs, st.lp_work)
 
 
 def _decode_step(tm, st: DecodeState, cos, sin, opts) -> None:
@@ -156,11 +165,17 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
              input_ids: Optional[torch.Tensor] = None, max_new_tokens: int = 20, do_sample: bool = False,
              num_beams: int = 1, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
-             use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False, **unused):
+             use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False,
+             output_logprobs: bool = False, **unused):
     """transformers `generate` for the greedy case. With `inputs_embeds` only the NEW tokens are returned (as
     transformers does); with `input_ids` the prompt is prepended and, like transformers, takes part in the repetition
     penalty and n-gram ban. Finished rows emit pad_token_id; generation stops when every row has produced eos or after
-    max_new_tokens."""
+    max_new_tokens.
+    output_logprobs=True returns (ids, logprobs[, stats]): logprobs f32 [B, n_new], one entry per NEW token (no entry for prompt
+    columns), trimmed at the same stop column as the ids. An entry is the log-probability of the emitted id under the model's own
+    distribution - log_softmax of the RAW logits, before the repetition penalty and the n-gram ban (transformers'
+    compute_transition_scores on `output_logits`) - so with either processor on, an emitted id need not be the raw argmax. The step
+    that emits a row's eos carries that token's log-probability; every later (pad) step of the row is exactly 0.0."""
     if do_sample or num_beams != 1:
         raise NotImplementedError("only greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use")
     if (inputs_embeds is None) == (input_ids is None):
@@ -189,7 +204,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
                 pad=0 if pad_token_id is None else int(pad_token_id))
     n_prompt = L0 if input_ids is not None else 0
     Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64)
-    st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens)
+    st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens, logprob_cols=max_new_tokens if output_logprobs else 0, prompt_cols=n_prompt)
     if input_ids is not None:
         st.generated[:, :L0] = input_ids
         st.step.fill_(L0)
@@ -204,9 +219,10 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     if max_new_tokens > 1 and use_graph:
         # warm the allocator, then capture one step; replay mutates the same state tensors
         side = torch.cuda.Stream(device=dev)
-        snap = None
+        mutated = snap = None
         if st.persistent is not None:            # what the step mutates, should it have to be redone on the other route (see below)
-            snap = (st.lens.clone(), st.step.clone(), st.finished.clone(), st.next_ids.clone(), st.generated.clone())
+            mutated = [st.lens, st.step, st.finished, st.next_ids, st.generated] + ([st.lp_done] if st.logprobs is not None else [])
+            snap = [t.clone() for t in mutated]
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             _decode_step(tm, st, cos, sin, opts)
@@ -221,7 +237,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
             warnings.warn("vq3: the persistent decode kernel's workgroups were not co-resident (a grid-barrier wait ran out); this "
                           "generate() call continues with one launch per projection (VQ3_DECODE_PERSISTENT=0 selects that route up front)")
             st.persistent = None
-            for dst, src in zip((st.lens, st.step, st.finished, st.next_ids, st.generated), snap):
+            for dst, src in zip(mutated, snap):
                 dst.copy_(src)
             _decode_step(tm, st, cos, sin, opts)
         elif st.persistent is not None:
@@ -256,6 +272,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
         if int(first.max()) < (1 << 30):
             stop = min(done_steps, int(first.max()) + 1)
     out = gen[:, : n_prompt + stop].to(dev)
+    ret = (out,) if st.logprobs is None else (out, st.logprobs[:, :stop].clone())
     if return_stats:
-        return out, {"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None}
-    return out
+        ret += ({"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None},)
+    return ret[0] if len(ret) == 1 else ret

@@ -781,6 +781,52 @@ def decode_advance(lens: Optional[torch.Tensor], B: int, step: Optional[torch.Te
     check(_lib.load().vq3_decode_advance(_p(lens), B, _p(step), _stream()), "vq3_decode_advance")
 
 
+LOGPROB_MAX_ROWS = 65535        # rows per vq3_token_logprob call (the row index is the grid's y)
+LOGPROB_WORK_PER_ROW = 192      # four-byte slots of scratch per row when the vocabulary is split (include/vq3_hip.h: vq3_token_logprob)
+
+
+def token_logprob(logits: torch.Tensor, targets: torch.Tensor, V: int, n: Optional[int] = None, slices: int = 0,
+                  want_lse: bool = True, want_rank: bool = True, work: Optional[torch.Tensor] = None):
+    """(logprob f32 [n], lse f32 [n] or None, rank i32 [n] or None) of the first n rows of bf16 logits [>= n, ld] over their first V
+    columns (vq3_token_logprob): logprob[i] = logits[i, targets[i]] - logsumexp(logits[i, :V]); a target outside [0, V) gives 0.0 and
+    rank -1. The logits are only read. slices: 0 = automatic, 1 = one workgroup per row, 2..64 = the split shape."""
+    _req(logits, BF16, "token_logprob logits"); _req(targets, torch.int32, "token_logprob targets")
+    n = logits.shape[0] if n is None else n
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] >= n and targets.is_contiguous() and targets.numel() >= n
+    dev = logits.device
+    lp = torch.empty(n, device=dev, dtype=F32)
+    lse = torch.empty(n, device=dev, dtype=F32) if want_lse else None
+    rank = torch.empty(n, device=dev, dtype=torch.int32) if want_rank else None
+    if work is None and slices != 1:
+        work = torch.empty(max(n, 1) * LOGPROB_WORK_PER_ROW, device=dev, dtype=F32)
+    if work is not None:
+        _req(work, F32, "token_logprob work")
+        assert slices == 1 or work.numel() >= n * LOGPROB_WORK_PER_ROW
+    check(_lib.load().vq3_token_logprob(logits.data_ptr(), logits.stride(0), n, V, targets.data_ptr(), lp.data_ptr(), _p(lse), _p(rank),
+                                        _p(work), int(slices), _stream()), "vq3_token_logprob")
+    return lp, lse, rank
+
+
+def token_logprob_step(logits: torch.Tensor, V: int, next_ids: torch.Tensor, step: torch.Tensor, prompt_offset: int,
+                       finished: torch.Tensor, done: torch.Tensor, logprob: torch.Tensor, work: torch.Tensor,
+                       rank: Optional[torch.Tensor] = None) -> None:
+    """After greedy_pick, before decode_advance: logprob[b, step - prompt_offset] = log p(next_ids[b]) under logits[b, :V]
+    (vq3_token_logprob_step), exactly 0.0 for a row that had finished before the pick. done (i32 [B], zero before the first step) is
+    the kernel's record of the finished flags before the pick; every per-step quantity is read on the device."""
+    _req(logits, BF16, "logprob_step logits"); _req(next_ids, torch.int32, "logprob_step next_ids"); _req(step, torch.int32, "logprob_step step")
+    _req(finished, torch.int32, "logprob_step finished"); _req(done, torch.int32, "logprob_step done")
+    _req(logprob, F32, "logprob_step logprob"); _req(work, F32, "logprob_step work")
+    B = logits.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logprob.dim() == 2 and logprob.is_contiguous() and logprob.shape[0] == B
+    assert next_ids.numel() >= B and finished.numel() >= B and done.numel() >= B and work.numel() >= B * LOGPROB_WORK_PER_ROW
+    if rank is not None:
+        _req(rank, torch.int32, "logprob_step rank")
+        assert rank.is_contiguous() and rank.shape == logprob.shape
+    check(_lib.load().vq3_token_logprob_step(logits.data_ptr(), logits.stride(0), B, V, next_ids.data_ptr(), step.data_ptr(),
+                                             int(prompt_offset), finished.data_ptr(), done.data_ptr(), logprob.data_ptr(), _p(rank),
+                                             logprob.shape[1], work.data_ptr(), _stream()), "vq3_token_logprob_step")
+
+
 def decode_layers_supported(hidden: int, intermediate: int, Hq: int, Hkv: int, head_dim: int, Lmax: int) -> bool:
     """True when vq3_qwen_decode_layers (all decoder layers of a B = 1 decode step in one persistent launch) takes this shape on this device."""
     return bool(_lib.load().vq3_qwen_decode_layers_supported(hidden, intermediate, Hq, Hkv, head_dim, Lmax))

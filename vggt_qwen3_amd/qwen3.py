@@ -626,6 +626,79 @@ class Qwen3ForCausalLM(nn.Module):
                      c.hidden_size, self.vocab_p)
         return out[:, : self.vocab]
 
+    SCORE_CHUNK_ROWS = 2048     # labelled rows per lm_head pass of score(): [2048, vocab_p] bf16 logits are 0.6 GB at Qwen3-4B
+
+    @staticmethod
+    def score_rows(labels: torch.Tensor, Lp: int):
+        """score()'s label alignment, the shift of label_rows: position t predicts labels[b, t + 1]. For labels [B, L] and hidden rows
+        laid out [B * Lp, H] (Lp >= L) returns, in row-major order of (b, t): the hidden rows that predict a label (i32 [n]), their
+        targets (i32 [n]) and the flat index into a [B, L] result where each one's score belongs (b * L + t + 1, i64 [n])."""
+        B, L = labels.shape
+        pos = (labels[:, 1:] != -100).nonzero(as_tuple=False)
+        b, t = pos[:, 0], pos[:, 1]
+        return (b * Lp + t).to(torch.int32), labels[b, t + 1].to(torch.int32), b * L + t + 1
+
+    @torch.no_grad()
+    def score(self, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+              labels: Optional[torch.Tensor] = None, input_ids: Optional[torch.Tensor] = None, chunk_rows: Optional[int] = None) -> dict:
+        """Teacher-forced log-probabilities (what transformers callers take from the forward's `logits` with log_softmax + gather):
+        one forward without saved context, then final RMSNorm + tied lm_head + vq3_token_logprob on the labelled rows only, at most
+        chunk_rows (default SCORE_CHUNK_ROWS, at most 65535: the kernel's rows per call) of them at a time - the results do not depend
+        on the chunking. Returns
+          logprobs    f32 [B, L]  log p(labels[b, t] | tokens < t); 0 where labels[b, t] == -100 and at t = 0
+          ranks       i32 [B, L]  tokens the model ranks above labels[b, t] (0 = it is the greedy pick); -1 where ignored
+          sum_logprob f32 [B], n_tokens i64 [B]
+        labels default to input_ids where attended. Dropout (LoRA) is off whatever self.training says; nothing is kept for a backward."""
+        if (inputs_embeds is None) == (input_ids is None):
+            raise ValueError("pass exactly one of inputs_embeds / input_ids")
+        dev = self.flat_w.device
+        self._pass_weights_gate()
+        if input_ids is not None:
+            input_ids = input_ids.to(dev)
+            embeds = self.get_input_embeddings()(input_ids)
+        else:
+            embeds = inputs_embeds.to(dev, BF16)
+        B, L, H = embeds.shape
+        if attention_mask is None:
+            attention_mask = torch.ones((B, L), device=dev, dtype=torch.int64)
+        attention_mask = attention_mask.to(dev)
+        if labels is None:
+            if input_ids is None:
+                raise ValueError("score: labels are required with inputs_embeds")
+            labels = torch.where(attention_mask != 0, input_ids, torch.full_like(input_ids, -100))
+        labels = labels.to(dev)
+        if tuple(labels.shape) != (B, L):
+            raise ValueError(f"score: labels must be [{B}, {L}], got {tuple(labels.shape)}")
+        cap = int(chunk_rows or self.SCORE_CHUNK_ROWS)
+        if cap < 1:
+            raise ValueError("score: chunk_rows must be >= 1")
+        cap = min(cap, ops.LOGPROB_MAX_ROWS)
+        was_training = self.training
+        self.training = False           # (forward_hidden hands self.training to the LoRA dropout)
+        try:
+            h_last, saved = self.forward_hidden(embeds, attention_mask, save=False)
+        finally:
+            self.training = was_training
+        idx, tgt, dest = self.score_rows(labels, saved["L"])
+        n = int(idx.numel())
+        logprobs = torch.zeros(B * L, device=dev, dtype=F32)
+        ranks = torch.full((B * L,), -1, device=dev, dtype=torch.int32)
+        c = self.config
+        logits = torch.empty((round_up(min(cap, n), 8), self.vocab_p), device=dev, dtype=BF16) if n else None
+        for r0 in range(0, n, cap):
+            m = min(cap, n - r0)
+            m8 = round_up(m, 8)
+            hs = ops.gather_rows(h_last, idx[r0:r0 + m].contiguous(), m, m8)
+            hn = ops.rmsnorm_fwd(hs, self._w["norm"], c.rms_norm_eps)
+            ops.gemm_raw(hn, self._w["embed"], logits, m, self.vocab, H, H, H, self.vocab_p)
+            # one workgroup per row whatever m is: the automatic choice goes by the row count, and the two launch shapes sum in
+            # different orders, so a row's bits would depend on the size of the chunk it fell into
+            lp, _, rk = ops.token_logprob(logits, tgt[r0:r0 + m].contiguous(), self.vocab, n=m, slices=1, want_lse=False)
+            logprobs[dest[r0:r0 + m]] = lp
+            ranks[dest[r0:r0 + m]] = rk
+        logprobs, ranks = logprobs.view(B, L), ranks.view(B, L)
+        return dict(logprobs=logprobs, ranks=ranks, sum_logprob=logprobs.sum(1), n_tokens=(ranks >= 0).sum(1))
+
     # ------------------------------------------------------------------ deferred weight gradients
     # dW = sum over the window's micro-batches of dY_j^T . X_j is ONE product over the concatenated token rows: [dY_1; dY_2; ..]^T .
     # [X_1; X_2; ..]. Run per micro-batch (contraction = 1200 rows) every weight-gradient GEMM re-reads and re-writes its whole bf16

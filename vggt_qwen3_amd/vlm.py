@@ -472,10 +472,11 @@ class VGGTQwen3VLM(nn.Module):
 
     # ------------------------------------------------------------------ forward / backward
     def forward_state(self, images, geom_token, input_ids, attention_mask, labels, need_grad: bool, loss_groups=None,
-                      graphs: bool = False) -> dict:
+                      graphs: bool = False, embeds_only: bool = False) -> dict:
         """Runs the whole path on the HIP kernels and returns a state dict with `loss` (+ what backward needs).
         loss_groups (sample counts): the batch is several micro-batches concatenated; `loss` is then the vector of their losses and
-        the backward differentiates their sum (Qwen3ForCausalLM.loss_head)."""
+        the backward differentiates their sum (Qwen3ForCausalLM.loss_head).
+        embeds_only: stop after the vision splice and return the text model's inputs (emb, attention_mask, labels, trimmed alike) - score()."""
         tm = self.text_model
         H = tm.config.hidden_size
         input_ids = input_ids.to(self.device_)
@@ -540,6 +541,8 @@ class VGGTQwen3VLM(nn.Module):
                 L = L_eff
         self._last_L = L
         emb = ops.embed_splice_fwd(input_ids.contiguous(), tm._w["embed"], feats16, srcmap, B, L, H, S)
+        if embeds_only:
+            return dict(emb=emb.view(B, L, H), attention_mask=attention_mask, labels=labels, B=B, L=L)
         if graphs and not need_grad:
             Lp_ = (L + 7) // 8 * 8
             h_last = self._graph_call(("text", B, L, bool(getattr(tm, "_fp8", None) is not None)), [emb.view(B, L, H), attention_mask.contiguous()],
@@ -665,6 +668,30 @@ class VGGTQwen3VLM(nn.Module):
             geom_in = _GeomBridge.apply(self, st, *[self.geom_head[0].weight, self.geom_head[0].bias,
                                                     self.geom_head[2].weight, self.geom_head[2].bias])
         return _TextLossFn.apply(self, st, geom_in, *params)
+
+
+    @torch.no_grad()
+    def score(self, images, geom_token, input_ids, attention_mask, labels, chunk_rows: Optional[int] = None) -> dict:
+        """Teacher-forced per-token log-probabilities of `labels` for forward()'s arguments: the same vision splice, then
+        Qwen3ForCausalLM.score on the spliced embeddings; returns its dict (logprobs / ranks [B, L], sum_logprob / n_tokens [B]) at the
+        caller's sequence length. Evaluation only: every module runs in eval mode for the call (dropout off) and is put back as it
+        was, nothing is saved for a backward and no gradient buffer is touched. (As a forward pass it consumes a pending
+        prefetch_images() result for the same tensor and sets _last_L.)"""
+        modes = [(m, m.training) for m in self.modules()]
+        for m, _ in modes:
+            m.training = False
+        try:
+            st = self.forward_state(images, geom_token, input_ids, attention_mask, labels, need_grad=False, embeds_only=True)
+            out = self.text_model.score(inputs_embeds=st["emb"], attention_mask=st["attention_mask"], labels=st["labels"],
+                                        chunk_rows=chunk_rows)
+        finally:
+            for m, was in modes:
+                m.training = was
+        B, L, Lt = st["B"], labels.shape[1], st["L"]
+        if Lt < L:      # trim_padding cut columns that carry neither a token nor a label: their entries are the ignored ones
+            out["logprobs"] = torch.cat([out["logprobs"], out["logprobs"].new_zeros((B, L - Lt))], dim=1)
+            out["ranks"] = torch.cat([out["ranks"], out["ranks"].new_full((B, L - Lt), -1)], dim=1)
+        return out
 
 
 class _GeomBridge(torch.autograd.Function):
