@@ -414,6 +414,28 @@ int vq3_greedy_pick(const void* logits_bf16, int64_t ld_logits, float* work, int
                     int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
                     int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
                     void* stream);
+/* The sampling twin of vq3_greedy_pick (replaces GenerationMixin._sample with do_sample=True: the two processors above, then
+ * TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper and the draw): same logits, same state, same bookkeeping (the final
+ * kernel is shared), every per-step quantity read from device memory. With z_i the f32 logit after the penalty and the ban, exactly as
+ * vq3_greedy_pick forms it, and s_i = z_i / temperature:
+ *   top-k   i is kept iff fewer than top_k ids have s_j > s_i (ties at the k-th value are all kept); 0 = off.
+ *   top-p   after top-k, q = softmax of s over the top-k set: i is kept iff the q_j of the ids with s_j > s_i sum to < top_p. Ids of
+ *           equal s stand or fall together, the maximum is always kept, and top_p = 1 keeps the whole top-k set.
+ *   An id whose z is -inf (banned) or NaN is never kept. Logits are expected to be finite or -inf.
+ *   draw    id = argmax over the kept ids of s_i + g_i, smallest index on an exact tie; g_i = -log(-log(u_i)),
+ *           u_i = ((r_i >> 8) + 0.5) * 2^-24, r_i = word (i & 3) of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *           (i >> 2, *step, b, 0), b the row index (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85).
+ *           u has 24 bits, so g lies in about [-2.9, 17.3]: an id more than ~e^-20 below the maximum is never drawn.
+ * The pick is a function of (logits, generated[b, :*step], the options, seed, *step, b) alone: integer counts and fixed-order sums, no
+ * dependence on the order in which atomics land. temperature > 0, top_k >= 0, 0 < top_p <= 1.
+ * work: as vq3_greedy_pick. sample_work: B * VQ3_SAMPLE_WORK_PER_ROW four-byte slots, 16-byte aligned, ZERO before the first call and
+ * owned by this entry from then on (each call leaves it zero where the next one needs it). n_kept (i32 [B]) / min_kept (f32 [B]) may be
+ * NULL: the size of the row's kept set and its smallest kept s (+inf for an empty set). */
+#define VQ3_SAMPLE_WORK_PER_ROW 65552
+int vq3_sample_pick(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
+                    int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty, int32_t no_repeat_ngram,
+                    const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids, float temperature, int32_t top_k,
+                    float top_p, uint64_t seed, void* sample_work, int32_t* n_kept, float* min_kept, void* stream);
 /* lens[b] += 1 for b < B (B <= 64), *step += 1 (either pointer may be NULL): the last launch of a decode step. */
 int vq3_decode_advance(int32_t* lens, int32_t B, int32_t* step, void* stream);
 /* Per-token log-probabilities of bf16 logits [n, ld] with V valid columns (replaces transformers `output_logits` / the forward's

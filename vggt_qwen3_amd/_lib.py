@@ -118,6 +118,8 @@ SIGNATURES = {
     "vq3_qwen_decode_qkprep": [c_p] * 9 + [i32, i32, i32, i32, i32, f32, c_p],
     "vq3_qwen_decode_attn": [c_p] * 5 + [i32, i32, i32, i32, i32, f32, c_p],
     "vq3_greedy_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, c_p],
+    "vq3_sample_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, f32, i32, f32, C.c_uint64, c_p, c_p,
+                        c_p, c_p],
     "vq3_decode_advance": [c_p, i32, c_p, c_p],
     "vq3_token_logprob": [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p],
     "vq3_token_logprob_step": [c_p, i64, i32, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p],

@@ -11,6 +11,7 @@
 //  * vq3_greedy_pick        repetition penalty -> n-gram ban -> argmax -> eos/pad bookkeeping, one workgroup per row.
 //  * vq3_decode_advance     lens[b]++, step++ (single thread; runs last in the step).
 #include "common.h"
+#include "pick.h"
 #include "vq3_hip.h"
 
 namespace {
@@ -306,6 +307,15 @@ extern "C" int vq3_greedy_pick(const void* logits_bf16, int64_t ld_logits, float
                      step, finished, eos_ids, n_eos, (long)pad_id, next_ids);
   VQ3_CHECK_LAUNCH("greedy_pick");
   return 0;
+}
+
+// the bookkeeping half of a pick for sample.hip, which brings its own phase 1 (pick.h)
+static_assert(PICK_NCH == vq3pick::PICK_SLICES && PICK_OVL / 2 == vq3pick::PICK_MAX_IDS, "pick.h restates this file's constants");
+void vq3pick::launch_pick_final(const float* pval, const int32_t* pidx, int64_t* generated, int max_new, const int32_t* step,
+                                int32_t* finished, const int64_t* eos_ids, int n_eos, long pad_id, int32_t* next_ids, int B,
+                                hipStream_t stream) {
+  hipLaunchKernelGGL(greedy_pick_final_kernel, dim3(B), dim3(64), 0, stream, pval, pidx, generated, max_new, step, finished, eos_ids,
+                     n_eos, pad_id, next_ids);
 }
 
 extern "C" int vq3_decode_advance(int32_t* lens, int32_t B, int32_t* step, void* stream) {

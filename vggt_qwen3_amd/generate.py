@@ -1,4 +1,5 @@
-"""Greedy generation on the HIP kernels with a resident KV cache - the surface the reference's inference scripts use:
+"""Generation on the HIP kernels with a resident KV cache: generate(), the greedy surface the reference's inference scripts use, and
+sample(), its seeded temperature / top-k / top-p twin (transformers' do_sample=True) with several draws per prompt:
 `model.text_model.generate(inputs_embeds=, attention_mask=, max_new_tokens=, do_sample=False, num_beams=1,
 repetition_penalty=, no_repeat_ngram_size=, eos_token_id=, pad_token_id=)` (src/inference/qa_inference.py:207-216,
 arkit_inference.py:274-284) plus the vision-token INSERTION splice those scripts perform before calling it
@@ -57,7 +58,7 @@ def _row_spans(attention_mask: torch.Tensor) -> List[Tuple[int, int]]:
 class DecodeState:
     """Device-resident state of one generate() call."""
 
-    def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0):
+    def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0, sampling: bool = False):
         c, dev = tm.config, tm.flat_w.device
         self.B, self.Lmax = B, Lmax
         nl = c.num_hidden_layers
@@ -69,6 +70,8 @@ class DecodeState:
         self.next_ids = torch.zeros(B, device=dev, dtype=torch.int32)
         self.generated = torch.zeros((B, gen_cols), device=dev, dtype=torch.int64)
         self.work = torch.zeros(B * 128 + 8, device=dev, dtype=F32)     # pick partials + overflow flag
+        # sample(): the histogram workspace of vq3_sample_pick (zero now; every pick leaves it zero again)
+        self.sample_work = ops.sample_workspace(B, dev) if sampling else None
         # output_logprobs: one f32 per new token, the kernel's own record of the finished flags before each pick, its partials
         self.logprobs = None
         if logprob_cols > 0:
@@ -90,34 +93,41 @@ class DecodeState:
                 status=torch.zeros(1, device=dev, dtype=torch.int32))
 
 
-def _prefill(tm, st: DecodeState, embeds: torch.Tensor, spans: Sequence[Tuple[int, int]]) -> torch.Tensor:
+def _prefill(tm, st: DecodeState, embeds: torch.Tensor, spans: Sequence[Tuple[int, int]], n_draws: int = 1) -> torch.Tensor:
     """Run the prompt through the training-path forward (batched MFMA GEMMs) and keep K/V. Rows of equal length go in
-    one pass; otherwise row by row, each without its padding. Returns the last prompt position's hidden state [B, H]."""
+    one pass; otherwise row by row, each without its padding. Prompt row b fills the n_draws cache rows b * n_draws ..: its K/V rows
+    and last hidden state are copied, the prompt is computed once. Returns the last prompt position's hidden state [B * n_draws, H]."""
     B, H = embeds.shape[0], embeds.shape[2]
     groups = {}
     for b, (lo, n) in enumerate(spans):
         groups.setdefault(n, []).append(b)
-    h_last = torch.empty((B, H), device=embeds.device, dtype=BF16)
+    h_last = torch.empty((B * n_draws, H), device=embeds.device, dtype=BF16)
+    rep = (lambda t: t) if n_draws == 1 else (lambda t: t.repeat_interleave(n_draws, dim=0))
     for n, rows in groups.items():
         x = torch.stack([embeds[b, spans[b][0]:spans[b][0] + n] for b in rows], dim=0).contiguous()
         mask = torch.ones((len(rows), n), device=embeds.device, dtype=torch.int64)
         h, saved = tm.forward_hidden(x, mask, save=True)
         Lp = saved["L"]
-        idx = torch.tensor(rows, device=embeds.device)
+        idx = torch.tensor([b * n_draws + j for b in rows for j in range(n_draws)], device=embeds.device)
         for i, ctx in enumerate(saved["layers"]):
-            st.K[i, idx, :, :n] = ctx["K"][:, :, :n]
-            st.V[i, idx, :, :n] = ctx["V"][:, :, :n]
-        h_last[idx] = h.view(len(rows), Lp, H)[:, n - 1]
+            st.K[i, idx, :, :n] = rep(ctx["K"][:, :, :n])
+            st.V[i, idx, :, :n] = rep(ctx["V"][:, :, :n])
+        h_last[idx] = rep(h.view(len(rows), Lp, H)[:, n - 1])
         del saved
-    st.lens.copy_(torch.tensor([n for _, n in spans], dtype=torch.int32))
+    st.lens.copy_(torch.tensor([n for _, n in spans for _ in range(n_draws)], dtype=torch.int32))
     return h_last
 
 
 def _logits_and_pick(tm, st: DecodeState, h: torch.Tensor, opts) -> None:
     c = tm.config
     logits = ops.skinny_linear(h, tm._w["embed"], n=tm.vocab, ln_w=tm._w["norm"], eps=c.rms_norm_eps)
-    ops.greedy_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
-                    opts["pad"], st.next_ids, tm.vocab)
+    sm = opts.get("sample")
+    if sm is None:
+        ops.greedy_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
+                        opts["pad"], st.next_ids, tm.vocab)
+    else:
+        ops.sample_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
+                        opts["pad"], st.next_ids, tm.vocab, sm["temperature"], sm["top_k"], sm["top_p"], sm["seed"], st.sample_work)
     if st.logprobs is not None:     # the raw logits' log-probability of the id just picked, into column step - prompt_cols
         ops.token_logprob_step(logits, tm.vocab, st.next_ids, st.step, st.prompt_cols, st.finished, st.lp_done, st.logprobs, st.lp_work)
 
@@ -177,7 +187,60 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     compute_transition_scores on `output_logits`) - so with either processor on, an emitted id need not be the raw argmax. The step
     that emits a row's eos carries that token's log-probability; every later (pad) step of the row is exactly 0.0."""
     if do_sample or num_beams != 1:
-        raise NotImplementedError("only greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use")
+        raise NotImplementedError("generate() is greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use; "
+                                  "sample() draws with temperature / top-k / top-p; there is no beam search")
+    return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1)
+
+
+def _check_sample_args(temperature, top_k, top_p, num_return_sequences, n_prompts) -> None:
+    """sample()'s own arguments; host arithmetic only."""
+    if not (temperature > 0 and temperature < float("inf")):
+        raise ValueError(f"sample: temperature must be > 0 and finite, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"sample: top_k must be an integer >= 0 (0 turns it off), got {top_k}")
+    if not (0 < top_p <= 1):
+        raise ValueError(f"sample: top_p must be in (0, 1], got {top_p}")
+    if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+        raise ValueError(f"sample: num_return_sequences must be an integer >= 1, got {num_return_sequences}")
+    if n_prompts * num_return_sequences > 8:
+        raise ValueError(f"sample: at most 8 rows per call (skinny GEMM width), got {n_prompts} prompts x {num_return_sequences} draws")
+
+
+@torch.no_grad()
+def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+           input_ids: Optional[torch.Tensor] = None, max_new_tokens: int = 20, repetition_penalty: float = 1.0,
+           no_repeat_ngram_size: int = 0, eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
+           use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False, output_logprobs: bool = False,
+           temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
+           **unused):
+    """transformers `generate(do_sample=True)`: every keyword of generate() above with the same meaning (same processors, same
+    eos / pad handling, same return values, output_logprobs included), the pick drawn instead of maximised (vq3_sample_pick, inside
+    the captured step like the greedy pick). After the repetition penalty and the n-gram ban, with s = logit / temperature:
+      top_k   keeps an id iff fewer than top_k ids score higher (ties at the k-th score all stay; 0 = off; 50 is transformers' default);
+      top_p   then keeps an id iff the softmax mass, over the top-k set, of the ids that score higher is < top_p (ids of equal score
+              stand or fall together, the best id always stays; without ties this is TopPLogitsWarper);
+      draw    Gumbel-max over what is left, noise from Philox4x32-10 keyed by `seed`, counted by (id, step, output row).
+    The noise has 24 bits: g = -log(-log(u)) lies in about [-2.9, 17.3], so an id more than ~e^-20 below the best score is never drawn.
+    A draw depends on (logits, ids so far, seed, step, row) only: the same seed gives the same ids on every run, with or without the
+    HIP graph, on either step route. seed=None takes a 64-bit seed from torch's default CPU generator (torch.manual_seed governs it);
+    return_stats reports the seed used.
+    num_return_sequences = n draws n continuations of every prompt row: output row b * n + j is draw j of prompt b (transformers'
+    order), B * n <= 8. Each prompt is prefilled once; its K/V rows and last hidden state are copied to its n cache rows.
+    output_logprobs=True: an entry is log_softmax of the RAW logits at the sampled id (compute_transition_scores on `output_logits`),
+    not the probability the id was drawn with after the warpers."""
+    shape_src = inputs_embeds if inputs_embeds is not None else input_ids
+    _check_sample_args(temperature, top_k, top_p, num_return_sequences, 0 if shape_src is None else int(shape_src.shape[0]))
+    if seed is None:
+        seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
+    sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, int(num_return_sequences))
+
+
+def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
+         pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, n_draws):
+    """The body of generate() (sampling None, n_draws 1) and sample(): prefill, one eager pick, then the decode steps."""
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if max_new_tokens < 1:
@@ -194,6 +257,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     if attention_mask is None:
         attention_mask = torch.ones((B, L0), device=dev, dtype=torch.int64)
     spans = _row_spans(attention_mask)
+    B *= n_draws                                # output rows: n_draws per prompt row, prompt-major
     eos = None
     if eos_token_id is not None:
         eos_list = [eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id)
@@ -201,15 +265,16 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
         if pad_token_id is None:
             pad_token_id = eos_list[0]          # transformers' fallback (with a warning)
     opts = dict(penalty=float(repetition_penalty), ngram=int(no_repeat_ngram_size), eos=eos,
-                pad=0 if pad_token_id is None else int(pad_token_id))
+                pad=0 if pad_token_id is None else int(pad_token_id), sample=sampling)
     n_prompt = L0 if input_ids is not None else 0
     Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64)
-    st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens, logprob_cols=max_new_tokens if output_logprobs else 0, prompt_cols=n_prompt)
+    st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens, logprob_cols=max_new_tokens if output_logprobs else 0, prompt_cols=n_prompt,
+                     sampling=sampling is not None)
     if input_ids is not None:
-        st.generated[:, :L0] = input_ids
+        st.generated[:, :L0] = input_ids.repeat_interleave(n_draws, dim=0)
         st.step.fill_(L0)
     cos, sin = tm.rope(Lmax)
-    h_last = _prefill(tm, st, embeds, spans)
+    h_last = _prefill(tm, st, embeds, spans, n_draws)
     _logits_and_pick(tm, st, h_last, opts)
     ops.decode_advance(None, B, st.step)
     if use_graph is None:
@@ -274,5 +339,8 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     out = gen[:, : n_prompt + stop].to(dev)
     ret = (out,) if st.logprobs is None else (out, st.logprobs[:, :stop].clone())
     if return_stats:
-        ret += ({"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None},)
+        stats = {"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None}
+        if sampling is not None:
+            stats["seed"] = sampling["seed"]
+        ret += (stats,)
     return ret[0] if len(ret) == 1 else ret

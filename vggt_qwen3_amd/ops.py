@@ -777,6 +777,37 @@ def greedy_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids
                                       _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), _stream()), "vq3_greedy_pick")
 
 
+SAMPLE_WORK_PER_ROW = 65552     # four-byte slots of vq3_sample_pick's workspace per row (include/vq3_hip.h: VQ3_SAMPLE_WORK_PER_ROW)
+
+
+def sample_workspace(B: int, device) -> torch.Tensor:
+    """vq3_sample_pick's workspace for B rows: zero, as the entry needs it before its first call (it keeps it so afterwards)."""
+    return torch.zeros(B * SAMPLE_WORK_PER_ROW, device=device, dtype=torch.int32)
+
+
+def sample_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids, pad_id, next_ids, V, temperature, top_k, top_p, seed,
+                sample_work, n_kept: Optional[torch.Tensor] = None, min_kept: Optional[torch.Tensor] = None) -> None:
+    """greedy_pick's sampling twin (vq3_sample_pick): repetition penalty -> n-gram ban -> temperature -> top-k -> top-p -> a
+    Philox / Gumbel-max draw keyed by (seed, *step, row), then the same bookkeeping. sample_work: sample_workspace(B, device);
+    n_kept (i32 [B]) / min_kept (f32 [B]), when given, receive the size of each row's kept set and its smallest kept logit / temperature."""
+    _req(logits, BF16, "pick logits"); _req(work, F32, "pick work"); _req(generated, torch.int64, "pick generated")
+    _req(step, torch.int32, "pick step"); _req(finished, torch.int32, "pick finished"); _req(next_ids, torch.int32, "pick next")
+    _req(sample_work, torch.int32, "pick sample_work")
+    B = logits.shape[0]
+    assert logits.stride(1) == 1 and work.numel() >= B * 128 + 1 and generated.is_contiguous() and generated.shape[0] == B
+    assert sample_work.is_contiguous() and sample_work.numel() >= B * SAMPLE_WORK_PER_ROW
+    if n_kept is not None:
+        _req(n_kept, torch.int32, "pick n_kept"); assert n_kept.is_contiguous() and n_kept.numel() >= B
+    if min_kept is not None:
+        _req(min_kept, F32, "pick min_kept"); assert min_kept.is_contiguous() and min_kept.numel() >= B
+    n_eos = 0 if eos_ids is None else int(eos_ids.numel())
+    check(_lib.load().vq3_sample_pick(logits.data_ptr(), logits.stride(0), work.data_ptr(), B, V, generated.data_ptr(),
+                                      generated.shape[1], step.data_ptr(), finished.data_ptr(), float(penalty), int(ngram),
+                                      _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), float(temperature), int(top_k),
+                                      float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, sample_work.data_ptr(), _p(n_kept), _p(min_kept),
+                                      _stream()), "vq3_sample_pick")
+
+
 def decode_advance(lens: Optional[torch.Tensor], B: int, step: Optional[torch.Tensor]) -> None:
     check(_lib.load().vq3_decode_advance(_p(lens), B, _p(step), _stream()), "vq3_decode_advance")
 

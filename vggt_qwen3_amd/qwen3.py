@@ -389,6 +389,12 @@ class Qwen3ForCausalLM(nn.Module):
         self._pass_weights_gate()
         return _generate(self, *args, **kwargs)
 
+    def sample(self, *args, **kwargs):
+        """Seeded temperature / top-k / top-p decoding with a KV cache, n draws per prompt (vggt_qwen3_amd/generate.py: sample)."""
+        from .generate import sample as _sample
+        self._pass_weights_gate()
+        return _sample(self, *args, **kwargs)
+
     # ------------------------------------------------------------------ helpers
     def rope(self, L: int):
         """cos/sin tables as HF builds them: fp32 angles, cat(freqs, freqs), cast to bf16 (modeling_qwen3.py:104-146).
