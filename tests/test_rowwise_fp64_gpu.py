@@ -13,7 +13,8 @@ Case -> branch:
                             VQ3_RMSNORM_BWD_ROWS 4 -> RB = 4, 8 / 16 / 256 -> the RB = 0 run-time path; the raw vq3_rmsnorm_bwd entry;
                             dres None / given; accumulate; defer= + colsum_flush bit-identical to the direct column sum
   test_colsum[nrows]        nrows 1..130 -> the r + 48 < nrows loop against its tail; 1024 / 1025 / 9600 -> nsplit 2 / 2 / 18 and the ticket
-                            clear (two launches in a row); cols 8, 72 -> cols % 64 != 0; 8 jobs of different cols -> the early return
+                            clear (two launches in a row); cols 8, 72 -> cols % 64 != 0; 8 jobs of different cols -> the early return;
+                            nrows 1, 17, 130 at cols 8, 200 -> colsum_kernel<float> rounded to bf16 == colsum_kernel<bf16_t> (one body)
   test_layernorm_fwd[cols]  4..1024 -> NCH 4, 1028..2048 -> 8, 4096 -> 16, 4100 / 8192 -> generic NCH 0; 252, 1028, 4100 -> cols % 256 != 0
   test_layernorm_bwd[cols]  4..1024 -> NCH 4, 2048 -> 8, 4096 -> 16; rows 1, 13, 17, 19, 1029 -> rows % 16 in 1..3 and waves that break early
   test_qkprep[case]         (32, 8, 2, 301): Qwen3-4B heads, B L % 8 = 2 -> the t >= T break; (5, 3, 1, 33) and (1, 1, 3, 5): odd HT, the
@@ -233,6 +234,14 @@ def test_colsum(ops, lib, nrows):
         ops.colsum_f32(part, out=vec(gf))
         gf.check("colsum_f32 random")
         R.check_colsum(f"colsum_f32 random {nrows}x{cols}", vec(gf), part, R.colsum_depth(nrows), out_bf16=False)
+    # the f32 and the bf16 entry are one body: the same additions in the same order, one round-to-nearest-even at the end
+    if nrows in (1, 17, 130):
+        for cols in (8, 200):
+            part = rnd((nrows, cols), nrows + cols, 1.0, F32)
+            g = Guard(1, cols)
+            check(lib.vq3_colsum_f32_to_bf16(part.data_ptr(), nrows, cols, g.t.data_ptr(), 0, stream()), "colsum")
+            g.check("colsum one body")
+            assert torch.equal(ops.colsum_f32(part).to(BF16), g.t[0]), f"colsum {nrows}x{cols}: bf16(vq3_colsum_f32) != vq3_colsum_f32_to_bf16"
 
 
 # ================================================================================================ LayerNorm

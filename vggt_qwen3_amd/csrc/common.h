@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // one MFMA A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
@@ -88,6 +90,23 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return t;
 }
 
+// A row walked by NT threads (a wave, by default) in chunks of W consecutive elements per thread: f(chunk index, the thread's first
+// column in that chunk). NCH > 0: NCH chunks, fully unrolled, a chunk past `cols` skipped - the form for rows that live in registers
+// indexed by the chunk. NCH == 0: any width, a run-time loop.
+template <int NCH, int W, int NT = 64, class F>
+__device__ __forceinline__ void for_chunks(int t, int cols, F&& f) {
+  if constexpr (NCH > 0) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int c = t * W + ch * NT * W;
+      if (c < cols) f(ch, c);
+    }
+  } else {
+    int ch = 0;
+    for (int c = t * W; c < cols; c += NT * W, ++ch) f(ch, c);
+  }
+}
+
 // Exact-form (erf) GELU, torch.nn.GELU()'s default, two values per VALU instruction: GELU(x) = x * Phi(x) with
 //   Phi(-a) = 2^q(a),  a = min(|x|, 5.5),  q = degree-7 fit of log2 Phi(-a) on [0, 5.5]      (Phi(x) = 1 - Phi(-x) for x > 0)
 // log2 Phi(-a) is smooth (it does not saturate as erf does), so 7 packed FMAs + one v_exp_f32 give |error| <= 7e-7 absolute and
@@ -164,6 +183,16 @@ void vq3_set_error(const char* fmt, ...);
       return 1;                             \
     }                                       \
   } while (0)
+
+// Host: the launch for a row of `need` chunks. f(std::integral_constant<int, NCH>) is called with the first NCH of the list that holds
+// the row (a 0 in the list is the any-width kernel); the entry's own argument check is what makes the last one fit.
+template <int NCH, int... More, class F>
+void for_nch(int need, F&& f) {
+  if constexpr (sizeof...(More) > 0) {
+    if (NCH != 0 && need > NCH) return for_nch<More...>(need, f);
+  }
+  f(std::integral_constant<int, NCH>{});
+}
 
 #define VQ3_CHECK_LAUNCH(name)                                                    \
   do {                                                                            \

@@ -165,62 +165,34 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const bf16_t* __restric
   const bf16_t* xr = x + r * ldx;
   uint8_t* qr = q + r * ldq;
   auto load8 = [&](int k, float (&f)[8]) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(xr + k);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f[2 * j] = __builtin_bit_cast(float, v[j] << 16);
-      f[2 * j + 1] = __builtin_bit_cast(float, v[j] & 0xffff0000u);
-    }
+    unpack8(*reinterpret_cast<const u32x4*>(xr + k), f);
     if (colmul) {
       const f32x4 c0 = *reinterpret_cast<const f32x4*>(colmul + k), c1 = *reinterpret_cast<const f32x4*>(colmul + k + 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { f[j] *= c0[j]; f[4 + j] *= c1[j]; }
     }
   };
-  auto store8 = [&](int k, const float (&f)[8], float inv) {
-    int w0 = 0, w1 = 0;
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, w0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, w0, true);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, w1, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, w1, true);
-    *reinterpret_cast<u32x2*>(qr + k) = u32x2{(unsigned)w0, (unsigned)w1};
-  };
+  float f[NCH > 0 ? NCH : 1][8];       // NCH == 0: one chunk of registers, and the conversion pass reads the row again
   float amax = 0.f;
-  if constexpr (NCH > 0) {
-    float f[NCH][8];
+  for_chunks<NCH, 8, 256>(threadIdx.x, K, [&](int c, int k) {
+    float(&v)[8] = f[NCH > 0 ? c : 0];
+    load8(k, v);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int k = threadIdx.x * 8 + c * 2048;
-      if (k < K) {
-        load8(k, f[c]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[c][j]));
-      }
-    }
-    amax = block_max<4>(amax, red);
-    const float inv = amax > 0.f ? 448.0f / amax : 1.0f;
-    if (threadIdx.x == 0) scale[r] = amax > 0.f ? amax / 448.0f : 1.0f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int k = threadIdx.x * 8 + c * 2048;
-      if (k < K) store8(k, f[c], inv);
-    }
-  } else {
-    for (int k = threadIdx.x * 8; k < K; k += 2048) {
-      float f[8];
-      load8(k, f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    }
-    amax = block_max<4>(amax, red);
-    const float inv = amax > 0.f ? 448.0f / amax : 1.0f;
-    if (threadIdx.x == 0) scale[r] = amax > 0.f ? amax / 448.0f : 1.0f;
-    for (int k = threadIdx.x * 8; k < K; k += 2048) {
-      float f[8];
-      load8(k, f);
-      store8(k, f, inv);
-    }
-  }
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  });
+  amax = block_max<4>(amax, red);
+  const float inv = amax > 0.f ? 448.0f / amax : 1.0f;
+  if (threadIdx.x == 0) scale[r] = amax > 0.f ? amax / 448.0f : 1.0f;
+  for_chunks<NCH, 8, 256>(threadIdx.x, K, [&](int c, int k) {
+    float(&v)[8] = f[NCH > 0 ? c : 0];
+    if (NCH == 0) load8(k, v);
+    int w0 = 0, w1 = 0;
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, w0, false);
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w0, true);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, w1, false);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, w1, true);
+    *reinterpret_cast<u32x2*>(qr + k) = u32x2{(unsigned)w0, (unsigned)w1};
+  });
 }
 
 // dst[c, r] = src[r, c] for a matrix of BYTES (the e4m3 weights' W^T copies: the NT operand of the dgrad GEMMs): 64 x 64 tiles through
@@ -300,14 +272,10 @@ static int quant_rows_impl(const void* x_bf16, int64_t ldx, int64_t rows, int32_
                 "quant_fp8_rows: need K %% 8 == 0 and 8-aligned leading dimensions");
   VQ3_CHECK_ARG(rows < (1l << 31), "quant_fp8_rows: too many rows");
   VQ3_CHECK_ARG(!colmul || (uintptr_t)colmul % 16 == 0, "quant_fp8_rows: colmul must be 16-byte aligned");
-#define VQ3_QUANT_LAUNCH(NCH)                                                                                          \
-  hipLaunchKernelGGL(vq3gemm::quant_rows_kernel<NCH>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream,       \
-                     (const bf16_t*)x_bf16, (long)ldx, K, (uint8_t*)q, (long)ldq, scale, colmul)
-  if (K <= 2 * 2048) VQ3_QUANT_LAUNCH(2);
-  else if (K <= 5 * 2048) VQ3_QUANT_LAUNCH(5);
-  else if (K <= 10 * 2048) VQ3_QUANT_LAUNCH(10);
-  else VQ3_QUANT_LAUNCH(0);
-#undef VQ3_QUANT_LAUNCH
+  for_nch<2, 5, 10, 0>((K - 1) / 2048 + 1, [&](auto nch) {
+    hipLaunchKernelGGL(vq3gemm::quant_rows_kernel<decltype(nch)::value>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x_bf16, (long)ldx, K, (uint8_t*)q, (long)ldq, scale, colmul);
+  });
   VQ3_CHECK_LAUNCH("quant_fp8_rows");
   return 0;
 }
@@ -368,7 +336,7 @@ extern "C" int vq3_gemm_fp8_ex(const vq3_gemm_fp8_desc* d, void* stream) {
     return 0;
   }
   VQ3_CHECK_ARG(d->mode == 0, "gemm_fp8_ex: the fused SwiGLU epilogues need the 256 x 256 kernel's contract (16-byte aligned rows)");
-  // plain product without column scales on the loader-ring kernel: a vector of ones stands in
+  // a plain product without column scales has no other kernel: the loader-ring kernels read a w_scale vector
   vq3_set_error("gemm_fp8_ex: mode 0 without w_scale needs 16-byte aligned bf16 rows");
   return 1;
 }

@@ -56,15 +56,9 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
                                                           long rows, int cols, int rb_rows) {
   extern __shared__ __attribute__((aligned(16))) float dw_s[];   // [4 waves][NCH * 512]
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float dwacc[NCH][8];
+  float dwacc[NCH][8] = {};
   bf16x8 wv[NCH];
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) {
-    const int c = lane * 8 + ch * 512;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dwacc[ch][j] = 0.f;
-    if (c < cols) wv[ch] = *reinterpret_cast<const bf16x8*>(w + c);
-  }
+  for_chunks<NCH, 8>(lane, cols, [&](int ch, int c) { wv[ch] = *reinterpret_cast<const bf16x8*>(w + c); });
   const int nrb = RB > 0 ? RB : rb_rows;              // (4, the default, as a constant: one pass, every load of the row at the top - as a
                                                       // run-time trip count the same kernel measured 73 us against 51)
   for (int rr = 0; rr < nrb / 4; ++rr) {              // nrb rows per workgroup (= per partial dw row), one row per wave and pass
@@ -77,58 +71,42 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
     const bf16_t* rr_ = dres ? dres + row * (long)cols : nullptr;
     float dot = 0.f;
     // all three row operands are requested up front: the residual-gradient read otherwise waits behind the row reduction
+    for_chunks<NCH, 8>(lane, cols, [&](int ch, int c) {
+      xv[ch] = *reinterpret_cast<const bf16x8*>(xr + c);
+      gv[ch] = *reinterpret_cast<const bf16x8*>(gr + c);
+      if (rr_) rv[ch] = *reinterpret_cast<const bf16x8*>(rr_ + c);
+    });
+    for_chunks<NCH, 8>(lane, cols, [&](int ch, int) {
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c = lane * 8 + ch * 512;
-      if (c < cols) {
-        xv[ch] = *reinterpret_cast<const bf16x8*>(xr + c);
-        gv[ch] = *reinterpret_cast<const bf16x8*>(gr + c);
-        if (rr_) rv[ch] = *reinterpret_cast<const bf16x8*>(rr_ + c);
+      for (int j = 0; j < 8; ++j) {
+        const float xh = bf2f((bf16_t)xv[ch][j]) * rs;
+        const float d = bf2f((bf16_t)gv[ch][j]);
+        dot += d * bf2f((bf16_t)wv[ch][j]) * xh;
+        dwacc[ch][j] += d * xh;
       }
-    }
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c = lane * 8 + ch * 512;
-      if (c < cols) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float xh = bf2f((bf16_t)xv[ch][j]) * rs;
-          const float d = bf2f((bf16_t)gv[ch][j]);
-          dot += d * bf2f((bf16_t)wv[ch][j]) * xh;
-          dwacc[ch][j] += d * xh;
-        }
-      }
-    }
+    });
     dot = wave_sum(dot) / (float)cols;
     bf16_t* dxr = dx + row * (long)cols;
+    for_chunks<NCH, 8>(lane, cols, [&](int ch, int c) {
+      bf16x8 o;
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c = lane * 8 + ch * 512;
-      if (c < cols) {
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float xh = bf2f((bf16_t)xv[ch][j]) * rs;
-          const float g = bf2f((bf16_t)gv[ch][j]) * bf2f((bf16_t)wv[ch][j]);
-          float d = rs * (g - xh * dot);
-          if (rr_) d += bf2f((bf16_t)rv[ch][j]);
-          o[j] = (short)f2bf(d);
-        }
-        *reinterpret_cast<bf16x8*>(dxr + c) = o;
+      for (int j = 0; j < 8; ++j) {
+        const float xh = bf2f((bf16_t)xv[ch][j]) * rs;
+        const float g = bf2f((bf16_t)gv[ch][j]) * bf2f((bf16_t)wv[ch][j]);
+        float d = rs * (g - xh * dot);
+        if (rr_) d += bf2f((bf16_t)rv[ch][j]);
+        o[j] = (short)f2bf(d);
       }
-    }
+      *reinterpret_cast<bf16x8*>(dxr + c) = o;
+    });
   }
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) {
-    const int c = lane * 8 + ch * 512;
-    if (c < cols) {
-      // LDS image [wave][chunk][half][lane][4]: a wave instruction writes 64 x 16 contiguous bytes (lane-major rows of 8 floats put
-      // lanes l and l + 4 on the same banks: conflict share 0.75 in profiles/r3_pmc_mfma_lds.csv)
-      float* base = dw_s + wid * (NCH * 512) + ch * 512 + lane * 4;
-      *reinterpret_cast<f32x4*>(base) = f32x4{dwacc[ch][0], dwacc[ch][1], dwacc[ch][2], dwacc[ch][3]};
-      *reinterpret_cast<f32x4*>(base + 256) = f32x4{dwacc[ch][4], dwacc[ch][5], dwacc[ch][6], dwacc[ch][7]};
-    }
-  }
+  for_chunks<NCH, 8>(lane, cols, [&](int ch, int) {
+    // LDS image [wave][chunk][half][lane][4]: a wave instruction writes 64 x 16 contiguous bytes (lane-major rows of 8 floats put
+    // lanes l and l + 4 on the same banks: conflict share 0.75 in profiles/r3_pmc_mfma_lds.csv)
+    float* base = dw_s + wid * (NCH * 512) + ch * 512 + lane * 4;
+    *reinterpret_cast<f32x4*>(base) = f32x4{dwacc[ch][0], dwacc[ch][1], dwacc[ch][2], dwacc[ch][3]};
+    *reinterpret_cast<f32x4*>(base + 256) = f32x4{dwacc[ch][4], dwacc[ch][5], dwacc[ch][6], dwacc[ch][7]};
+  });
   __syncthreads();
   float* out = dw + (long)blockIdx.x * cols;
   for (int i = threadIdx.x; i < NCH * 512; i += 256) {          // image index -> column: chunk i / 512, half (i / 256) & 1, lane (i & 255) / 4
@@ -137,16 +115,15 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
   }
 }
 
-// out_bf16[c] (+)= sum_r part[r][c]: 64 columns per block, 16 waves stride over the rows (4 independent loads in
-// flight per lane), LDS combine.
-__global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ part, int nrows, int cols,
-                                                      bf16_t* __restrict__ out, int accumulate) {
-  __shared__ float red[16][64];
+// ---------------------------------------------------------------- column sums
+// Column c's sum over the rows r0 .. nrows - 1 of part[.][cols], for a workgroup of 16 waves on 64 columns: the waves stride over the
+// rows (4 independent loads in flight per lane, (a0 + a1) + (a2 + a3)), LDS combine, and wave 0 adds the 16 terms in wave order.
+// True in the lanes that hold a column's sum in v: wave 0's, where c < cols.
+__device__ __forceinline__ bool colsum_walk(const float* __restrict__ part, int r0, int nrows, int cols, int c, float (&red)[16][64], float& v) {
   const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   if (c < cols) {
-    int r = rg;
+    int r = r0 + rg;
     for (; r + 48 < nrows; r += 64) {
       a0 += part[(long)r * cols + c];
       a1 += part[(long)(r + 16) * cols + c];
@@ -157,13 +134,32 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
   }
   red[rg][lane] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (rg == 0 && c < cols) {
-    float v = 0.f;
+  if (rg != 0 || c >= cols) return false;
+  v = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) v += red[i][lane];
+  for (int i = 0; i < 16; ++i) v += red[i][lane];
+  return true;
+}
+// out[c] (+)= v, out in f32 or rounded to bf16
+template <class T>
+__device__ __forceinline__ void colsum_finish(T* out, int c, float v, int accumulate) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (accumulate) v += out[c];
+    out[c] = v;
+  } else {
     if (accumulate) v += bf2f(out[c]);
     out[c] = f2bf(v);
   }
+}
+
+// out[c] (+)= sum_r part[r][c], T = bf16_t (the text model's gradients) or float (the Perceiver's parameters and gradients are fp32):
+// 64 columns per block
+template <class T>
+__global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ part, int nrows, int cols, T* __restrict__ out, int accumulate) {
+  __shared__ float red[16][64];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  float v;
+  if (colsum_walk(part, 0, nrows, cols, c, red, v)) colsum_finish(out, c, v, accumulate);
 }
 
 // Several column sums in ONE launch (blockIdx.y = job): a decoder layer's backward leaves four partial slabs (two RMSNorm
@@ -190,29 +186,12 @@ __global__ __launch_bounds__(1024) void colsum_multi_kernel(ColsumJobs jobs) {
   const int chunk = ((jobs.nrows[job] + nsplit - 1) / nsplit + 15) / 16 * 16;
   const int r0 = sp * chunk;
   const int nrows = jobs.nrows[job] < r0 + chunk ? jobs.nrows[job] : r0 + chunk;       // this workgroup walks rows r0 .. nrows - 1
-  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (c < cols) {
-    int r = r0 + rg;
-    for (; r + 48 < nrows; r += 64) {
-      a0 += part[(long)r * cols + c];
-      a1 += part[(long)(r + 16) * cols + c];
-      a2 += part[(long)(r + 32) * cols + c];
-      a3 += part[(long)(r + 48) * cols + c];
-    }
-    for (; r < nrows; r += 16) a0 += part[(long)r * cols + c];
-  }
-  red[rg][lane] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   float v = 0.f;
-  if (rg == 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v += red[i][lane];
-  }
+  const bool mine = colsum_walk(part, r0, nrows, cols, c, red, v);      // this lane finishes column c
   if (nsplit > 1) {
     float* sc = jobs.scratch + ((long)job * CS_MAX_SPLIT) * CS_MAX_COLS;
-    if (rg == 0 && c < cols) __hip_atomic_store(sc + (long)sp * CS_MAX_COLS + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (mine) __hip_atomic_store(sc + (long)sp * CS_MAX_COLS + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -224,14 +203,10 @@ __global__ __launch_bounds__(1024) void colsum_multi_kernel(ColsumJobs jobs) {
     __syncthreads();
     if (ticket_s != nsplit - 1) return;
     v = 0.f;
-    if (rg == 0 && c < cols)
+    if (mine)
       for (int s2 = 0; s2 < nsplit; ++s2) v += __hip_atomic_load(sc + (long)s2 * CS_MAX_COLS + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (rg == 0 && c < cols) {
-    bf16_t* out = jobs.out[job];
-    if (jobs.accumulate[job]) v += bf2f(out[c]);
-    out[c] = f2bf(v);
-  }
+  if (mine) colsum_finish(jobs.out[job], c, v, jobs.accumulate[job]);
 }
 
 // ---------------------------------------------------------------- LayerNorm forward
@@ -265,8 +240,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restri
       }
     }
   };
-  // rows of up to 256 * NCH * ... elements are read ONCE and kept in registers (NCH chunks of 4 per lane); NCH == 0 is the
-  // generic three-pass form for other widths
+  // rows of up to 256 * NCH elements are read ONCE and kept in registers (NCH chunks of 4 per lane); NCH == 0 is the generic form for
+  // other widths: one chunk of registers, and the second and third pass read the row again.
+  // The first pass keeps its two arms: on for_chunks hipcc 7.2 forms the row address and the `res_` test once per chunk, and
+  // <true, 16> takes 133 VGPRs against 114 - an occupancy step.
   float cache[NCH > 0 ? NCH : 1][4];
   float s = 0.f;
   if (NCH > 0) {
@@ -280,37 +257,25 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restri
     }
   } else {
     for (int c = lane * 4; c < cols; c += 256) {
-      float v[4];
-      ldrow(c, v);
-      s += v[0] + v[1] + v[2] + v[3];
+      ldrow(c, cache[0]);
+      s += cache[0][0] + cache[0][1] + cache[0][2] + cache[0][3];
     }
   }
   const float mean = wave_sum(s) / (float)cols;
   float q = 0.f;
-  if (NCH > 0) {
+  for_chunks<NCH, 4>(lane, cols, [&](int i, int c) {
+    float(&v)[4] = cache[NCH > 0 ? i : 0];
+    if (NCH == 0) ldrow(c, v);
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      if (lane * 4 + 256 * i < cols) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float d = cache[i][j] - mean;
-          q += d * d;
-        }
-      }
+    for (int j = 0; j < 4; ++j) {
+      const float d = v[j] - mean;
+      q += d * d;
     }
-  } else {
-    for (int c = lane * 4; c < cols; c += 256) {
-      float v[4];
-      ldrow(c, v);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = v[j] - mean;
-        q += d * d;
-      }
-    }
-  }
+  });
   const float rs = rsqrtf(wave_sum(q) / (float)cols + eps);
-  auto emit = [&](int c, const float (&v)[4]) {
+  for_chunks<NCH, 4>(lane, cols, [&](int i, int c) {
+    float(&v)[4] = cache[NCH > 0 ? i : 0];
+    if (NCH == 0) ldrow(c, v);
     const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
     const f32x4 bv = *reinterpret_cast<const f32x4*>(b + c);
     float o[4];
@@ -323,20 +288,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restri
       p[1] = pack2bf(o[2], o[3]);
       *reinterpret_cast<u32x2*>(y_bf16 + row * (long)cols + c) = p;
     }
-  };
-  if constexpr (NCH > 0) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane * 4 + 256 * i;
-      if (c < cols) emit(c, cache[i]);
-    }
-  } else {
-    for (int c = lane * 4; c < cols; c += 256) {
-      float v[4];
-      ldrow(c, v);
-      emit(c, v);
-    }
-  }
+  });
 }
 
 // ---------------------------------------------------------------- LayerNorm backward (Perceiver "train_projector" mode)
@@ -353,120 +305,65 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             int cols, float eps) {
   extern __shared__ float lnb_red[];               // [2][cols]
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float aw[NCH][4], ab[NCH][4];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { aw[c][j] = 0.f; ab[c][j] = 0.f; }
+  float aw[NCH][4] = {}, ab[NCH][4] = {};
   const float inv = 1.f / (float)cols;
   for (int rr = wid; rr < LNB_ROWS; rr += 4) {
     const long row = (long)blockIdx.x * LNB_ROWS + rr;
     if (row >= rows) break;
-    float xv[NCH][4], gv[NCH][4];
+    float xv[NCH][4] = {}, gv[NCH][4];
     float s = 0.f;
+    for_chunks<NCH, 4>(lane, cols, [&](int c, int col) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(x + row * (long)cols + col);
+      if (res) v += *reinterpret_cast<const f32x4*>(res + row * (long)cols + col);     // the forward normalised x + res
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = (c * 64 + lane) * 4;
-      if (col < cols) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(x + row * (long)cols + col);
-        if (res) v += *reinterpret_cast<const f32x4*>(res + row * (long)cols + col);     // the forward normalised x + res
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { xv[c][j] = v[j]; s += v[j]; }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xv[c][j] = 0.f;
-      }
-    }
+      for (int j = 0; j < 4; ++j) { xv[c][j] = v[j]; s += v[j]; }
+    });
     const float mean = wave_sum(s) * inv;
     float sq = 0.f;
+    for_chunks<NCH, 4>(lane, cols, [&](int c, int) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = (c * 64 + lane) * 4;
-      if (col < cols) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { xv[c][j] -= mean; sq = fmaf(xv[c][j], xv[c][j], sq); }
-      }
-    }
+      for (int j = 0; j < 4; ++j) { xv[c][j] -= mean; sq = fmaf(xv[c][j], xv[c][j], sq); }
+    });
     const float rstd = rsqrtf(wave_sum(sq) * inv + eps);
     float sg = 0.f, sgx = 0.f;
+    for_chunks<NCH, 4>(lane, cols, [&](int c, int col) {
+      const f32x4 d = *reinterpret_cast<const f32x4*>(dy + row * (long)cols + col);
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = (c * 64 + lane) * 4;
-      if (col < cols) {
-        const f32x4 d = *reinterpret_cast<const f32x4*>(dy + row * (long)cols + col);
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          xv[c][j] *= rstd;                         // xhat
-          gv[c][j] = d[j] * wv[j];
-          sg += gv[c][j];
-          sgx = fmaf(gv[c][j], xv[c][j], sgx);
-          aw[c][j] = fmaf(d[j], xv[c][j], aw[c][j]);
-          ab[c][j] += d[j];
-        }
+      for (int j = 0; j < 4; ++j) {
+        xv[c][j] *= rstd;                         // xhat
+        gv[c][j] = d[j] * wv[j];
+        sg += gv[c][j];
+        sgx = fmaf(gv[c][j], xv[c][j], sgx);
+        aw[c][j] = fmaf(d[j], xv[c][j], aw[c][j]);
+        ab[c][j] += d[j];
       }
-    }
+    });
     const float mg = wave_sum(sg) * inv, mgx = wave_sum(sgx) * inv;
+    for_chunks<NCH, 4>(lane, cols, [&](int c, int col) {
+      f32x4 o;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = (c * 64 + lane) * 4;
-      if (col < cols) {
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = rstd * (gv[c][j] - mg - xv[c][j] * mgx);
-        *reinterpret_cast<f32x4*>(dx + row * (long)cols + col) = o;
-      }
-    }
+      for (int j = 0; j < 4; ++j) o[j] = rstd * (gv[c][j] - mg - xv[c][j] * mgx);
+      *reinterpret_cast<f32x4*>(dx + row * (long)cols + col) = o;
+    });
   }
   // combine the four waves' partial column sums (the waves add into one [2][cols] LDS image in turn), one partial row per workgroup
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (wid == k) {
+      for_chunks<NCH, 4>(lane, cols, [&](int c, int col) {
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int col = (c * 64 + lane) * 4;
-        if (col < cols) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            lnb_red[col + j] = (k ? lnb_red[col + j] : 0.f) + aw[c][j];
-            lnb_red[cols + col + j] = (k ? lnb_red[cols + col + j] : 0.f) + ab[c][j];
-          }
+        for (int j = 0; j < 4; ++j) {
+          lnb_red[col + j] = (k ? lnb_red[col + j] : 0.f) + aw[c][j];
+          lnb_red[cols + col + j] = (k ? lnb_red[cols + col + j] : 0.f) + ab[c][j];
         }
-      }
+      });
     }
     __syncthreads();
   }
   for (int col = threadIdx.x; col < cols; col += 256) {
     dw_part[(long)blockIdx.x * cols + col] = lnb_red[col];
     db_part[(long)blockIdx.x * cols + col] = lnb_red[cols + col];
-  }
-}
-
-// out_f32[c] (+)= sum_r part[r][c]  (the f32 twin of colsum_kernel: the Perceiver's parameters and gradients are fp32)
-__global__ __launch_bounds__(1024) void colsum_f32_kernel(const float* __restrict__ part, int nrows, int cols, float* __restrict__ out,
-                                                          int accumulate) {
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (c < cols) {
-    int r = rg;
-    for (; r + 48 < nrows; r += 64) {
-      a0 += part[(long)r * cols + c];
-      a1 += part[(long)(r + 16) * cols + c];
-      a2 += part[(long)(r + 32) * cols + c];
-      a3 += part[(long)(r + 48) * cols + c];
-    }
-    for (; r < nrows; r += 16) a0 += part[(long)r * cols + c];
-  }
-  red[rg][lane] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (rg == 0 && c < cols) {
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v += red[i][lane];
-    if (accumulate) v += out[c];
-    out[c] = v;
   }
 }
 
@@ -492,22 +389,16 @@ static int rmsnorm_bwd_impl(const void* dy, const void* x, const void* w, const 
   VQ3_CHECK_ARG(rows > 0 && cols > 0 && cols % 8 == 0 && cols <= 4096, "rmsnorm_bwd: bad cols=%d (<= 4096)", cols);
   VQ3_CHECK_ARG(rows_per_part >= 4 && rows_per_part <= 256 && rows_per_part % 4 == 0, "rmsnorm_bwd: rows_per_part=%d must be a multiple of 4 in 4..256", rows_per_part);
   const long nblk = (rows + rows_per_part - 1) / rows_per_part;
-#define VQ3_RB_LAUNCH(NCH)                                                                                           \
-  do {                                                                                                              \
-    if (rows_per_part == 4)                                                                                         \
-      hipLaunchKernelGGL((rmsnorm_bwd_kernel<NCH, 4>), dim3((unsigned)nblk), dim3(256), 4 * NCH * 512 * sizeof(float),     \
-                         (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd,           \
-                         (const bf16_t*)dres, (bf16_t*)dx, dw_f32, (long)rows, cols, 4);                            \
-    else                                                                                                            \
-      hipLaunchKernelGGL((rmsnorm_bwd_kernel<NCH, 0>), dim3((unsigned)nblk), dim3(256), 4 * NCH * 512 * sizeof(float),     \
-                         (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd,           \
-                         (const bf16_t*)dres, (bf16_t*)dx, dw_f32, (long)rows, cols, (int)rows_per_part);           \
-  } while (0)
-  if (cols <= 512) VQ3_RB_LAUNCH(1);
-  else if (cols <= 1024) VQ3_RB_LAUNCH(2);
-  else if (cols <= 2560) VQ3_RB_LAUNCH(5);
-  else VQ3_RB_LAUNCH(8);
-#undef VQ3_RB_LAUNCH
+  for_nch<1, 2, 5, 8>((cols - 1) / 512 + 1, [&](auto nch) {
+    auto launch = [&](auto rb) {
+      constexpr int NCH = decltype(nch)::value, RB = decltype(rb)::value;
+      hipLaunchKernelGGL((rmsnorm_bwd_kernel<NCH, RB>), dim3((unsigned)nblk), dim3(256), 4 * NCH * 512 * sizeof(float), (hipStream_t)stream,
+                         (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw_f32, (long)rows, cols,
+                         (int)rows_per_part);
+    };
+    if (rows_per_part == 4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 0>{});
+  });
   VQ3_CHECK_LAUNCH("rmsnorm_bwd");
   return 0;
 }
@@ -538,9 +429,9 @@ __global__ __launch_bounds__(256) void rowstats128_kernel(const bf16_t* __restri
     const u32x4 v = *reinterpret_cast<const u32x4*>(x + row * cols + c * 8);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float lo = bf2f((bf16_t)(v[k] & 0xffff)), hi = bf2f((bf16_t)(v[k] >> 16));
-      sm += lo + hi;
-      sq = fmaf(lo, lo, fmaf(hi, hi, sq));
+      const f32x2_t p = unpack2bf(v[k]);
+      sm += p[0] + p[1];
+      sq = fmaf(p[0], p[0], fmaf(p[1], p[1], sq));
     }
   }
 #pragma unroll
@@ -564,16 +455,14 @@ extern "C" int vq3_layernorm_fwd(const void* x, const void* res, int32_t x_f32, 
   VQ3_CHECK_ARG(x && w && b && (y_bf16 || y_f32), "layernorm_fwd: null pointer");
   VQ3_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0, "layernorm_fwd: cols=%d must be a positive multiple of 4", cols);
   const long nblk = (rows + 3) / 4;
-  const int nch = cols <= 1024 ? 4 : (cols <= 2048 ? 8 : (cols <= 4096 ? 16 : 0));
-#define VQ3_LN(F32, N)                                                                                                   \
-  hipLaunchKernelGGL((layernorm_fwd_kernel<F32, N>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, x, res, w, b, \
-                     (bf16_t*)y_bf16, y_f32, (long)rows, cols, eps)
-  if (x_f32) {
-    if (nch == 4) VQ3_LN(true, 4); else if (nch == 8) VQ3_LN(true, 8); else if (nch == 16) VQ3_LN(true, 16); else VQ3_LN(true, 0);
-  } else {
-    if (nch == 4) VQ3_LN(false, 4); else if (nch == 8) VQ3_LN(false, 8); else if (nch == 16) VQ3_LN(false, 16); else VQ3_LN(false, 0);
-  }
-#undef VQ3_LN
+  for_nch<4, 8, 16, 0>((cols - 1) / 256 + 1, [&](auto nch) {
+    auto launch = [&](auto f32) {
+      hipLaunchKernelGGL((layernorm_fwd_kernel<decltype(f32)::value, decltype(nch)::value>), dim3((unsigned)nblk), dim3(256), 0,
+                         (hipStream_t)stream, x, res, w, b, (bf16_t*)y_bf16, y_f32, (long)rows, cols, eps);
+    };
+    if (x_f32) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
   VQ3_CHECK_LAUNCH("layernorm_fwd");
   return 0;
 }
@@ -636,18 +525,17 @@ extern "C" int vq3_layernorm_bwd(const float* dy, const float* x, const float* r
   VQ3_CHECK_ARG((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)res | (uintptr_t)w | (uintptr_t)dx) % 16) == 0, "layernorm_bwd: pointers must be 16-byte aligned");
   const long nblk = (rows + LNB_ROWS - 1) / LNB_ROWS;
   const size_t smem = (size_t)2 * cols * sizeof(float);
-#define VQ3_LNB(N)                                                                                                          \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<N>), dim3((unsigned)nblk), dim3(256), smem, (hipStream_t)stream, dy, x, res, w, dx, dw_part, \
-                     db_part, (long)rows, cols, eps)
-  if (cols <= 1024) VQ3_LNB(4); else if (cols <= 2048) VQ3_LNB(8); else VQ3_LNB(16);
-#undef VQ3_LNB
+  for_nch<4, 8, 16>((cols - 1) / 256 + 1, [&](auto nch) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(nch)::value>), dim3((unsigned)nblk), dim3(256), smem, (hipStream_t)stream, dy, x, res, w, dx,
+                       dw_part, db_part, (long)rows, cols, eps);
+  });
   VQ3_CHECK_LAUNCH("layernorm_bwd");
   return 0;
 }
 
 extern "C" int vq3_colsum_f32(const float* part, int32_t nrows, int32_t cols, float* out_f32, int32_t accumulate, void* stream) {
   VQ3_CHECK_ARG(part && out_f32 && nrows > 0 && cols > 0, "colsum_f32: bad args");
-  hipLaunchKernelGGL(colsum_f32_kernel, dim3((cols + 63) / 64), dim3(1024), 0, (hipStream_t)stream, part, nrows, cols, out_f32, accumulate);
+  hipLaunchKernelGGL(colsum_kernel<float>, dim3((cols + 63) / 64), dim3(1024), 0, (hipStream_t)stream, part, nrows, cols, out_f32, accumulate);
   VQ3_CHECK_LAUNCH("colsum_f32");
   return 0;
 }
@@ -655,7 +543,7 @@ extern "C" int vq3_colsum_f32(const float* part, int32_t nrows, int32_t cols, fl
 extern "C" int vq3_colsum_f32_to_bf16(const float* part, int32_t nrows, int32_t cols, void* out_bf16, int32_t accumulate,
                                       void* stream) {
   VQ3_CHECK_ARG(part && out_bf16 && nrows > 0 && cols > 0, "colsum: bad args");
-  hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64), dim3(1024), 0, (hipStream_t)stream, part, nrows, cols,
+  hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((cols + 63) / 64), dim3(1024), 0, (hipStream_t)stream, part, nrows, cols,
                      (bf16_t*)out_bf16, accumulate);
   VQ3_CHECK_LAUNCH("colsum_f32_to_bf16");
   return 0;
