@@ -495,6 +495,56 @@ int64_t vq3_qwen_decode_layers_workspace_bytes(void);
 int vq3_qwen_decode_layers_supported(int32_t hidden, int32_t intermediate, int32_t Hq, int32_t Hkv, int32_t head_dim, int32_t Lmax);
 int vq3_qwen_decode_layers(const vq3_decode_layers_desc* desc, void* stream);
 
+/* Beam search (transformers 5.15 GenerationMixin._beam_search, do_sample=False), the step that replaces the pick. R = n_prompts *
+ * num_beams rows (row b * num_beams + j is beam j of prompt b), R <= 8, n_prompts <= 4, 2 <= num_beams <= 8, n_eos <= 3; K =
+ * max(2, 1 + n_eos) * num_beams <= 32 candidates per prompt. From the bf16 logits [R, ld] of the running beams:
+ *   lp = log_softmax(f32(logits[:V])); repetition penalty ON THE LOG-PROBABILITIES (lp * p where lp < 0, else lp / p) over the ids of
+ *   the row's running sequence [0, *step); n-gram ban (-inf); acc = lp + run_score[row] (f32); per prompt the top K of the num_beams * V
+ *   values (higher first, then the smaller flat index parent * V + token; a -inf value is never a candidate); a candidate hits iff its
+ *   token is an eos id or *step + 1 == max_len; the next running beams are the top num_beams of acc + hit * -1e9 (ties: smaller rank);
+ *   the finished slots, the early-stopping heuristic and the loop condition follow _update_finished_beams,
+ *   _check_early_stop_heuristic and _beam_search_has_unfinished_sequences (early_stopping: 0 False, 1 True, 2 "never"; merge ties:
+ *   old slots first, then the smaller rank).
+ * State, all device memory, all read and written here: step i32 [1] = ids per row so far (read only; vq3_decode_advance moves it);
+ * run_seq / fin_seq i32 [R, max_len] (max_len <= 512 = prompt + new ids); run_score f32 [R] (0, -1e9, -1e9, ... per prompt before the
+ * first call); fin_score f32 [R] (-1e9 before the first call); fin_len i32 [R] (ids of a finished slot: fin_seq past it is not
+ * meaningful, nor is the fin_seq of a slot whose fin_flag is 0); fin_flag i32 [R] (0); heur i32 [n_prompts] (1); all_done i32 [1] (0),
+ * sticky: once set, a call changes NOTHING. Outputs: next_ids i32 [R] (last id of every new running beam), src_row i32 [R] (the row
+ * its sequence - and its K/V - continue), and row *step - prompt_len of trace_parent / trace_token i32, trace_score f32
+ * [trace_rows, R] (a row outside [0, trace_rows) is not written; NULL allowed). work: R * VQ3_BEAM_WORK_PER_ROW four-byte slots.
+ * No atomics, fixed reduction orders: the same bits run after run. */
+#define VQ3_BEAM_WORK_PER_ROW 4224
+typedef struct vq3_beam_step_desc {
+  const void* logits_bf16;
+  int64_t ld_logits;
+  const int32_t* step;
+  int32_t* run_seq;
+  float* run_score;
+  int32_t* fin_seq;
+  float* fin_score;
+  int32_t* fin_len;
+  int32_t* fin_flag;
+  int32_t* heur;
+  int32_t* all_done;
+  int32_t* next_ids;
+  int32_t* src_row;
+  int32_t* trace_parent;
+  int32_t* trace_token;
+  float* trace_score;
+  void* work;
+  int32_t V, n_prompts, num_beams, max_len, prompt_len, trace_rows;
+  int32_t no_repeat_ngram, n_eos, eos_ids[3], early_stopping;
+  float repetition_penalty, length_penalty;
+} vq3_beam_step_desc;
+int vq3_beam_step(const vq3_beam_step_desc* desc, void* stream);
+/* Make cache row r hold the K/V of row src_row[r] (rows of one prompt only; a value outside the prompt's rows counts as r), in place, on
+ * Kcache / Vcache [layers, R, Hkv, Lmax, 128] bf16, positions 0 .. lens[first row of the prompt] inclusive (the beams of a prompt share
+ * one length; positions past it are neither read nor written). A row with src_row[r] == r is not stored, a prompt whose map is the
+ * identity touches nothing. all_done (NULL allowed): when *all_done != 0 the call does nothing. Plain 16-byte loads and stores: a
+ * thread loads its piece of every source row of the prompt before it stores any, and no other thread touches those addresses. */
+int vq3_beam_reorder(void* Kcache, void* Vcache, const int32_t* src_row, const int32_t* lens, const int32_t* all_done, int32_t layers,
+                     int32_t n_prompts, int32_t num_beams, int32_t Hkv, int32_t Lmax, int32_t head_dim, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * FP8 forward GEMM (BASELINE config C5: Qwen3 linear weights in OCP e4m3, one fp32 scale per output channel;
  * activations quantised per token on the fly; fp32 accumulate). Replaces nn.Linear of modeling_qwen3.py:81-83,241-280.

@@ -53,6 +53,15 @@ class DecodeLayersDesc(C.Structure):
                 ("eps", f32), ("scale", f32)]
 
 
+class BeamStepDesc(C.Structure):
+    _fields_ = [("logits_bf16", c_p), ("ld_logits", i64), ("step", c_p), ("run_seq", c_p), ("run_score", c_p), ("fin_seq", c_p),
+                ("fin_score", c_p), ("fin_len", c_p), ("fin_flag", c_p), ("heur", c_p), ("all_done", c_p), ("next_ids", c_p),
+                ("src_row", c_p), ("trace_parent", c_p), ("trace_token", c_p), ("trace_score", c_p), ("work", c_p),
+                ("V", i32), ("n_prompts", i32), ("num_beams", i32), ("max_len", i32), ("prompt_len", i32), ("trace_rows", i32),
+                ("no_repeat_ngram", i32), ("n_eos", i32), ("eos_ids", i32 * 3), ("early_stopping", i32),
+                ("repetition_penalty", f32), ("length_penalty", f32)]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("part", c_p), ("out_bf16", c_p), ("nrows", i32), ("cols", i32), ("accumulate", i32)]
 
@@ -126,6 +135,8 @@ SIGNATURES = {
     "vq3_qwen_decode_layers_supported": [i32] * 6,
     "vq3_qwen_decode_layers_workspace_bytes": [],
     "vq3_qwen_decode_layers": [C.POINTER(DecodeLayersDesc), c_p],
+    "vq3_beam_step": [C.POINTER(BeamStepDesc), c_p],
+    "vq3_beam_reorder": [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, c_p],
     "vq3_quant_fp8_rows": [c_p, i64, i64, i32, c_p, i64, c_p, c_p],
     "vq3_gemm_fp8_nt": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i64, i64, i64, i64, c_p],
     "vq3_quant_fp8_rows_scaled": [c_p, i64, i64, i32, c_p, c_p, i64, c_p, c_p],

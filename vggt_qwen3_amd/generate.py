@@ -1,5 +1,6 @@
-"""Generation on the HIP kernels with a resident KV cache: generate(), the greedy surface the reference's inference scripts use, and
-sample(), its seeded temperature / top-k / top-p twin (transformers' do_sample=True) with several draws per prompt:
+"""Generation on the HIP kernels with a resident KV cache: generate(), the greedy surface the reference's inference scripts use,
+sample(), its seeded temperature / top-k / top-p twin (transformers' do_sample=True) with several draws per prompt, and beam_search()
+(transformers' num_beams > 1), whose step and cache reorder run on the device inside the same captured step:
 `model.text_model.generate(inputs_embeds=, attention_mask=, max_new_tokens=, do_sample=False, num_beams=1,
 repetition_penalty=, no_repeat_ngram_size=, eos_token_id=, pad_token_id=)` (src/inference/qa_inference.py:207-216,
 arkit_inference.py:274-284) plus the vision-token INSERTION splice those scripts perform before calling it
@@ -121,7 +122,13 @@ def _prefill(tm, st: DecodeState, embeds: torch.Tensor, spans: Sequence[Tuple[in
 def _logits_and_pick(tm, st: DecodeState, h: torch.Tensor, opts) -> None:
     c = tm.config
     logits = ops.skinny_linear(h, tm._w["embed"], n=tm.vocab, ln_w=tm._w["norm"], eps=c.rms_norm_eps)
-    sm = opts.get("sample")
+    sm, bm = opts.get("sample"), opts.get("beam")
+    if bm is not None:              # beam search: the beam step in the pick's place, then the cache rows follow the surviving beams
+        bs = bm["state"]
+        ops.beam_step(logits, tm.vocab, bs, st.step, st.next_ids, opts["penalty"], opts["ngram"], bm["eos"], bm["length_penalty"],
+                      bm["early_stopping"])
+        ops.beam_reorder(st.K, st.V, bs.src_row, st.lens, bs.n_prompts, bs.num_beams, bs.all_done)
+        return
     if sm is None:
         ops.greedy_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
                         opts["pad"], st.next_ids, tm.vocab)
@@ -188,7 +195,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     that emits a row's eos carries that token's log-probability; every later (pad) step of the row is exactly 0.0."""
     if do_sample or num_beams != 1:
         raise NotImplementedError("generate() is greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use; "
-                                  "sample() draws with temperature / top-k / top-p; there is no beam search")
+                                  "sample() draws with temperature / top-k / top-p; beam_search() searches with num_beams beams")
     return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
                 pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1)
 
@@ -343,4 +350,118 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
         if sampling is not None:
             stats["seed"] = sampling["seed"]
         ret += (stats,)
+    return ret[0] if len(ret) == 1 else ret
+
+
+def _check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id, n_prompts) -> List[int]:
+    """beam_search()'s own arguments; host arithmetic only. Returns the eos ids as a list."""
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not (2 <= num_beams <= ops.BEAM_MAX_ROWS):
+        raise ValueError(f"beam_search: num_beams must be an integer in 2..{ops.BEAM_MAX_ROWS}, got {num_beams}")
+    if n_prompts * num_beams > ops.BEAM_MAX_ROWS:
+        raise ValueError(f"beam_search: at most {ops.BEAM_MAX_ROWS} rows per call (skinny GEMM width), got {n_prompts} prompts x {num_beams} beams")
+    if int(num_return_sequences) != num_return_sequences or not (1 <= num_return_sequences <= num_beams):
+        raise ValueError(f"beam_search: num_return_sequences must be an integer in 1..num_beams, got {num_return_sequences}")
+    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+    if len(eos) > ops.BEAM_MAX_EOS:
+        raise ValueError(f"beam_search: at most {ops.BEAM_MAX_EOS} eos ids (32 candidates per prompt), got {len(eos)}")
+    if not any(early_stopping is v for v in (False, True)) and early_stopping != "never":
+        raise ValueError(f"beam_search: early_stopping must be False, True or 'never', got {early_stopping!r}")
+    if not (float("-inf") < length_penalty < float("inf")):
+        raise ValueError(f"beam_search: length_penalty must be finite, got {length_penalty}")
+    return eos
+
+
+@torch.no_grad()
+def beam_search(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+                input_ids: Optional[torch.Tensor] = None, max_new_tokens: int = 20, num_beams: int = 4, num_return_sequences: int = 1,
+                length_penalty: float = 1.0, early_stopping: Union[bool, str] = False, repetition_penalty: float = 1.0,
+                no_repeat_ngram_size: int = 0, eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
+                use_graph: Optional[bool] = None, check_every: int = 8, return_scores: bool = False, return_stats: bool = False):
+    """transformers `generate(num_beams=n, do_sample=False)` - GenerationMixin._beam_search of transformers 5.15, step for step: per
+    prompt n running beams, n finished slots and K = max(2, 1 + number of eos ids) * n candidates per step; the processors act on the
+    LOG-PROBABILITIES (log_softmax first, then repetition penalty and n-gram ban - unlike generate() / sample(), which apply them to the
+    raw logits); a hypothesis' score is its summed log-probability / length ** length_penalty; early_stopping False / True / "never"
+    as there. The beam step (vq3_beam_step) and the move of the K/V cache rows to the surviving beams (vq3_beam_reorder) run inside the
+    captured decode step; the host reads one `all_done` word every check_every steps. Each prompt is prefilled once and fanned out to
+    its n cache rows; B * n <= 8. Exact ties are ordered by the device's rule (higher score, then smaller beam * V + id, then smaller
+    candidate rank) where torch.topk's order is unspecified.
+    Returns `sequences` i64 [B * num_return_sequences, n_prompt + longest]: prompt-major, best first, cropped to the longest returned
+    hypothesis, pad_token_id (else the first eos id) past a shorter one's end; with inputs_embeds the new ids only. return_scores adds
+    `sequences_scores` f32; return_stats adds a dict with steps_run, graph, Lmax and the search trace the device recorded: parents /
+    tokens i32 and running_scores f32 [steps_run, B * n] - the parent row, last id and score of every running beam after each step -
+    and `finished`, the n finished slots of every prompt as the device holds them (sequences i32 [B * n, n_prompt + max_new_tokens],
+    lengths, scores, flags)."""
+    shape_src = inputs_embeds if inputs_embeds is not None else input_ids
+    eos_list = _check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id,
+                                0 if shape_src is None else int(shape_src.shape[0]))
+    if (inputs_embeds is None) == (input_ids is None):
+        raise ValueError("beam_search: pass exactly one of inputs_embeds / input_ids")
+    if max_new_tokens < 1:
+        raise ValueError("beam_search: max_new_tokens must be >= 1")
+    nb, nret = int(num_beams), int(num_return_sequences)
+    dev = tm.flat_w.device
+    if input_ids is not None:
+        input_ids = input_ids.to(dev)
+        embeds = tm.get_input_embeddings()(input_ids)
+    else:
+        embeds = inputs_embeds.to(dev, BF16)
+    Bp, L0, _ = embeds.shape
+    if attention_mask is None:
+        attention_mask = torch.ones((Bp, L0), device=dev, dtype=torch.int64)
+    spans = _row_spans(attention_mask)
+    R = Bp * nb
+    if pad_token_id is None:
+        pad_token_id = eos_list[0] if eos_list else 0       # without an eos every hypothesis has full length: nothing is filled
+    n_prompt = L0 if input_ids is not None else 0
+    max_len = n_prompt + max_new_tokens
+    Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64)
+    st = DecodeState(tm, R, Lmax, 1)
+    bs = ops.BeamState(Bp, nb, max_len, n_prompt, max_new_tokens, dev)
+    opts = dict(penalty=float(repetition_penalty), ngram=int(no_repeat_ngram_size), sample=None,
+                beam=dict(state=bs, eos=eos_list, length_penalty=float(length_penalty), early_stopping=early_stopping))
+    if input_ids is not None:
+        bs.run_seq[:, :L0] = input_ids.repeat_interleave(nb, dim=0).to(torch.int32)
+        st.step.fill_(L0)
+    cos, sin = tm.rope(Lmax)
+    h_last = _prefill(tm, st, embeds, spans, nb)
+    _logits_and_pick(tm, st, h_last, opts)
+    ops.decode_advance(None, R, st.step)
+    if use_graph is None:
+        use_graph = os.environ.get("VQ3_DECODE_GRAPH", "1") != "0"
+    graph = None
+    done_steps = 1
+    if max_new_tokens > 1 and use_graph:
+        side = torch.cuda.Stream(device=dev)                # warm the allocator, then capture one step; replay mutates the same state
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            _decode_step(tm, st, cos, sin, opts)
+        torch.cuda.current_stream().wait_stream(side)
+        done_steps += 1
+        if max_new_tokens > 2:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                _decode_step(tm, st, cos, sin, opts)
+    while done_steps < max_new_tokens:
+        # a search ends before max_new_tokens only through finished hypotheses, and those need an eos
+        if eos_list and (done_steps % check_every == 0 or graph is None) and bool(bs.all_done.item()):
+            break
+        if graph is not None:
+            graph.replay()
+        else:
+            _decode_step(tm, st, cos, sin, opts)
+        done_steps += 1
+    # the finished slots are kept best first: the first num_return_sequences of every prompt, cropped to the longest of them
+    steps_run = int((bs.trace_parent[:, 0] >= 0).sum())     # steps launched after all_done wrote nothing
+    fin_len = bs.fin_len.view(Bp, nb)[:, :nret].reshape(-1)
+    longest = int(fin_len.max())
+    out = bs.fin_seq.view(Bp, nb, max_len)[:, :nret].reshape(Bp * nret, max_len)[:, :longest].to(torch.int64)
+    out = torch.where(torch.arange(longest, device=dev)[None, :] < fin_len[:, None], out, torch.full_like(out, int(pad_token_id)))
+    ret = (out[:, n_prompt:] if input_ids is None else out,)
+    if return_scores:
+        ret += (bs.fin_score.view(Bp, nb)[:, :nret].reshape(-1).clone(),)
+    if return_stats:
+        ret += ({"steps_run": steps_run, "graph": graph is not None, "Lmax": Lmax, "parents": bs.trace_parent[:steps_run].clone(),
+                 "tokens": bs.trace_token[:steps_run].clone(), "running_scores": bs.trace_score[:steps_run].clone(),
+                 "finished": {"sequences": bs.fin_seq.clone(), "lengths": bs.fin_len.clone(), "scores": bs.fin_score.clone(),
+                              "flags": bs.fin_flag.clone()}},)
     return ret[0] if len(ret) == 1 else ret

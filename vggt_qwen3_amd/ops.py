@@ -812,6 +812,86 @@ def decode_advance(lens: Optional[torch.Tensor], B: int, step: Optional[torch.Te
     check(_lib.load().vq3_decode_advance(_p(lens), B, _p(step), _stream()), "vq3_decode_advance")
 
 
+BEAM_WORK_PER_ROW = 4224       # four-byte slots of vq3_beam_step's workspace per row (include/vq3_hip.h: VQ3_BEAM_WORK_PER_ROW)
+BEAM_MAX_ROWS, BEAM_MAX_PROMPTS, BEAM_MAX_EOS = 8, 4, 3
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+class BeamState:
+    """Device state of a beam search as vq3_beam_step keeps it (include/vq3_hip.h): R = n_prompts * num_beams rows, row b * num_beams + j
+    is beam j of prompt b. Fresh state is the start of a search: running scores 0, -1e9, ..., empty finished slots at -1e9."""
+
+    def __init__(self, n_prompts: int, num_beams: int, max_len: int, prompt_len: int, trace_rows: int, device):
+        R = n_prompts * num_beams
+        self.n_prompts, self.num_beams, self.max_len, self.prompt_len, self.R = n_prompts, num_beams, max_len, prompt_len, R
+        i = dict(device=device, dtype=torch.int32)
+        self.run_seq = torch.zeros((R, max_len), **i)
+        self.fin_seq = torch.zeros((R, max_len), **i)
+        self.run_score = torch.full((n_prompts, num_beams), -1.0e9, device=device, dtype=F32)
+        self.run_score[:, 0] = 0.0
+        self.run_score = self.run_score.reshape(R)
+        self.fin_score = torch.full((R,), -1.0e9, device=device, dtype=F32)
+        self.fin_len = torch.zeros(R, **i)
+        self.fin_flag = torch.zeros(R, **i)
+        self.heur = torch.ones(n_prompts, **i)
+        self.all_done = torch.zeros(1, **i)
+        self.src_row = torch.arange(R, **i)
+        self.trace_parent = torch.full((trace_rows, R), -1, **i)      # a row the device has not written: the step did not run
+        self.trace_token = torch.zeros((trace_rows, R), **i)
+        self.trace_score = torch.zeros((trace_rows, R), device=device, dtype=F32)
+        self.work = torch.zeros(R * BEAM_WORK_PER_ROW, device=device, dtype=F32)
+
+
+def beam_step(logits: torch.Tensor, V: int, bs: BeamState, step: torch.Tensor, next_ids: torch.Tensor, penalty: float, ngram: int,
+              eos_ids, length_penalty: float, early_stopping) -> None:
+    """One beam-search step (vq3_beam_step) on the bf16 logits [R, ld] of the running beams: the state in `bs` moves on by one id, next_ids
+    (i32 [R]) and bs.src_row receive the last id and the parent row of every new running beam. step (i32 [1]) is the number of ids per
+    row so far and is only read. eos_ids: a sequence of at most 3 ints."""
+    _req(logits, BF16, "beam logits"); _req(step, torch.int32, "beam step"); _req(next_ids, torch.int32, "beam next_ids")
+    R = bs.R
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == R and next_ids.is_contiguous() and next_ids.numel() >= R
+    for name in ("run_seq", "fin_seq", "fin_len", "fin_flag", "heur", "all_done", "src_row", "trace_parent", "trace_token"):
+        t = getattr(bs, name)
+        _req(t, torch.int32, f"beam {name}"); assert t.is_contiguous()
+    for name in ("run_score", "fin_score", "trace_score", "work"):
+        t = getattr(bs, name)
+        _req(t, F32, f"beam {name}"); assert t.is_contiguous()
+    assert bs.run_seq.shape == (R, bs.max_len) and bs.fin_seq.shape == (R, bs.max_len) and bs.work.numel() >= R * BEAM_WORK_PER_ROW
+    assert bs.trace_parent.shape == bs.trace_token.shape == bs.trace_score.shape and bs.trace_parent.shape[1] == R
+    eos = [] if eos_ids is None else [int(e) for e in eos_ids]
+    if len(eos) > BEAM_MAX_EOS:
+        raise _lib.Vq3Error(f"beam_step: at most {BEAM_MAX_EOS} eos ids, got {len(eos)}")
+    d = _lib.BeamStepDesc()
+    d.logits_bf16, d.ld_logits, d.step = logits.data_ptr(), logits.stride(0), step.data_ptr()
+    d.run_seq, d.run_score, d.fin_seq, d.fin_score = bs.run_seq.data_ptr(), bs.run_score.data_ptr(), bs.fin_seq.data_ptr(), bs.fin_score.data_ptr()
+    d.fin_len, d.fin_flag, d.heur, d.all_done = bs.fin_len.data_ptr(), bs.fin_flag.data_ptr(), bs.heur.data_ptr(), bs.all_done.data_ptr()
+    d.next_ids, d.src_row, d.work = next_ids.data_ptr(), bs.src_row.data_ptr(), bs.work.data_ptr()
+    rows = bs.trace_parent.shape[0]
+    if rows > 0:
+        d.trace_parent, d.trace_token, d.trace_score = bs.trace_parent.data_ptr(), bs.trace_token.data_ptr(), bs.trace_score.data_ptr()
+    d.V, d.n_prompts, d.num_beams, d.max_len, d.prompt_len, d.trace_rows = V, bs.n_prompts, bs.num_beams, bs.max_len, bs.prompt_len, rows
+    d.no_repeat_ngram, d.n_eos, d.early_stopping = int(ngram), len(eos), EARLY_STOPPING[early_stopping]
+    for k, e in enumerate(eos):
+        d.eos_ids[k] = e
+    d.repetition_penalty, d.length_penalty = float(penalty), float(length_penalty)
+    import ctypes
+    check(_lib.load().vq3_beam_step(ctypes.byref(d), _stream()), "vq3_beam_step")
+
+
+def beam_reorder(K: torch.Tensor, V: torch.Tensor, src_row: torch.Tensor, lens: torch.Tensor, n_prompts: int, num_beams: int,
+                 all_done: Optional[torch.Tensor] = None) -> None:
+    """In place on the caches [layers, R, Hkv, Lmax, 128]: row r <- row src_row[r] (rows of one prompt), positions 0 .. lens inclusive
+    (vq3_beam_reorder). Rows that keep their place are not stored; nothing happens once *all_done is set."""
+    _req(K, BF16, "beam_reorder K"); _req(V, BF16, "beam_reorder V"); _req(src_row, torch.int32, "beam_reorder src_row")
+    _req(lens, torch.int32, "beam_reorder lens")
+    assert K.dim() == 5 and K.shape == V.shape and K.is_contiguous() and V.is_contiguous() and K.shape[1] == n_prompts * num_beams
+    assert src_row.is_contiguous() and src_row.numel() >= K.shape[1] and lens.is_contiguous() and lens.numel() >= K.shape[1]
+    if all_done is not None:
+        _req(all_done, torch.int32, "beam_reorder all_done")
+    check(_lib.load().vq3_beam_reorder(K.data_ptr(), V.data_ptr(), src_row.data_ptr(), lens.data_ptr(), _p(all_done), K.shape[0], n_prompts,
+                                       num_beams, K.shape[2], K.shape[3], K.shape[4], _stream()), "vq3_beam_reorder")
+
+
 LOGPROB_MAX_ROWS = 65535        # rows per vq3_token_logprob call (the row index is the grid's y)
 LOGPROB_WORK_PER_ROW = 192      # four-byte slots of scratch per row when the vocabulary is split (include/vq3_hip.h: vq3_token_logprob)
 

@@ -395,6 +395,12 @@ class Qwen3ForCausalLM(nn.Module):
         self._pass_weights_gate()
         return _sample(self, *args, **kwargs)
 
+    def beam_search(self, *args, **kwargs):
+        """Beam search with a KV cache, the beam step and the cache reorder on the device (vggt_qwen3_amd/generate.py: beam_search)."""
+        from .generate import beam_search as _beam_search
+        self._pass_weights_gate()
+        return _beam_search(self, *args, **kwargs)
+
     # ------------------------------------------------------------------ helpers
     def rope(self, L: int):
         """cos/sin tables as HF builds them: fp32 angles, cat(freqs, freqs), cast to bf16 (modeling_qwen3.py:104-146).
