@@ -406,6 +406,22 @@ int vq3_qwen_decode_qkprep(const void* qkv, const void* q_w, const void* k_w, co
 /* O[b, h, :] = softmax(scale * q . K[b, h/G, :lens[b]+1]^T) . V[b, h/G, :lens[b]+1]  (GQA, fp32 softmax). */
 int vq3_qwen_decode_attn(const void* Q, const void* Kcache, const void* Vcache, const int32_t* lens, void* O, int32_t B,
                          int32_t Hq, int32_t Hkv, int32_t head_dim, int32_t Lmax, float scale, void* stream);
+/* A chunk of Ln new tokens per row behind a cached prefix - the cache path of modeling_qwen3.py:237-253 (`past_key_values`: q_norm /
+ * k_norm + RoPE at the positions after the prefix, then the cache update). qkv bf16 [B*Ln, (Hq+2Hkv)*128]; token t of row b sits at
+ * position lens[b] + t; Q bf16 [B, Hq, Ln, 128]; K, V written into the caches [B, Hkv, Lmax, 128] at rows lens[b] + t. lens, new_lens:
+ * i32 [B] in device memory; tokens t >= new_lens[b] are padding: nothing is cached, their Q rows are 0. Positions >= Lmax are never
+ * written. cos/sin: bf16 [>= Lmax, 128]. Bit-equal to vq3_qwen_qkprep_fwd on the same rows. Hq / Hkv <= 4; Lmax a multiple of 64,
+ * <= 12288; 1 <= Ln <= 8192. */
+int vq3_qwen_append_qkprep(const void* qkv, const void* q_w, const void* k_w, const void* cos, const void* sin,
+                           const int32_t* lens, const int32_t* new_lens, void* Q, void* Kcache, void* Vcache, int32_t B,
+                           int32_t Ln, int32_t Hq, int32_t Hkv, int32_t head_dim, int32_t Lmax, float eps, void* stream);
+/* Causal GQA attention of that chunk against the cache (modeling_qwen3.py:185-207,254-280 with `past_key_values`): query t of row b
+ * attends cache rows 0 .. lens[b] + t (lens BEFORE the chunk; the chunk's own K / V rows are already in the cache) and nothing else.
+ * Q as vq3_qwen_append_qkprep writes it; O bf16 token-major [B*Ln, Hq*128], row stride ldo elements - vq3_qwen_flash_fwd's layout;
+ * rows t >= new_lens[b] are exactly 0. No cache row at or past lens[b] + new_lens[b] is read. Same limits as the q/k prep. */
+int vq3_qwen_append_attn(const void* Q, const void* Kcache, const void* Vcache, const int32_t* lens, const int32_t* new_lens,
+                         void* O, int32_t B, int32_t Ln, int32_t Hq, int32_t Hkv, int32_t head_dim, int32_t Lmax, int64_t ldo,
+                         float scale, void* stream);
 /* transformers greedy step on bf16 logits [B, ld]: RepetitionPenaltyLogitsProcessor over generated[b, :*step], then
  * NoRepeatNGramLogitsProcessor, argmax (first index on ties), finished rows emit pad_id, eos marks a row finished.
  * Writes generated[b, *step] and next_ids[b]. work: scratch of >= B*128 + 1 four-byte slots; max_new (columns of

@@ -126,6 +126,8 @@ SIGNATURES = {
     "vq3_skinny_gemm_fp8": [c_p, c_p, c_p, c_p, c_p, c_p, f32, i32, i32, i32, i32, i64, i64, i64, i64, c_p],
     "vq3_qwen_decode_qkprep": [c_p] * 9 + [i32, i32, i32, i32, i32, f32, c_p],
     "vq3_qwen_decode_attn": [c_p] * 5 + [i32, i32, i32, i32, i32, f32, c_p],
+    "vq3_qwen_append_qkprep": [c_p] * 10 + [i32, i32, i32, i32, i32, i32, f32, c_p],
+    "vq3_qwen_append_attn": [c_p] * 6 + [i32, i32, i32, i32, i32, i32, i64, f32, c_p],
     "vq3_greedy_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, c_p],
     "vq3_sample_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, f32, i32, f32, C.c_uint64, c_p, c_p,
                         c_p, c_p],

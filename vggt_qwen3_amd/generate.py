@@ -12,6 +12,10 @@ computed and positions are 0..n-1 exactly as transformers derives them from the 
 GEMM; all step state is in device memory, so the whole step is captured once in a HIP graph and replayed per token -
 the host only checks the `finished` flags every few steps. One row at Qwen3-4B's shape (the reference's case): the 36
 layers of a step are ONE persistent launch (csrc/decode_layers.hip) + lm_head + pick; otherwise ~220 launches.
+
+Sessions (transformers' `past_key_values`): a KVCache keeps K/V between calls; extend() runs only the positions it does not hold yet
+against it (csrc/qwen_append.hip: a chunk of new positions over the resident cache) and generate(kv_cache=) / sample(kv_cache=)
+decode on its buffers - multi-turn sessions, chunked prefill, KVCache.truncate to roll a turn back.
 """
 from __future__ import annotations
 
@@ -56,16 +60,116 @@ def _row_spans(attention_mask: torch.Tensor) -> List[Tuple[int, int]]:
     return spans
 
 
+KV_MAX_CAPACITY = 12288     # rows per cache row: the decode attention's limit (csrc/decode.hip)
+
+
+class KVCache:
+    """A session's K/V - transformers' `past_key_values`: K, V bf16 [layers, batch, Hkv, capacity, 128], zero-initialised and laid out
+    as DecodeState's, so generate(kv_cache=) decodes on them in place. `capacity` is rounded up to 64. Row b holds the K/V of the first
+    lengths[b] positions of its sequence; `lens` is the same count as i32 on the device. What lies behind lengths[b] (pad steps decoded
+    after the row's eos, a turn rolled back) is never read and is overwritten by the next extend()."""
+
+    def __init__(self, tm, batch: int, capacity: int):
+        if batch < 1 or capacity < 1:
+            raise ValueError(f"KVCache: batch and capacity must be >= 1, got {batch}, {capacity}")
+        self.capacity = round_up(int(capacity), 64)
+        if self.capacity > KV_MAX_CAPACITY:
+            raise ValueError(f"KVCache: capacity {self.capacity} exceeds the decode attention's {KV_MAX_CAPACITY} rows")
+        c, dev = tm.config, tm.flat_w.device
+        self.batch = int(batch)
+        self.K = torch.zeros((c.num_hidden_layers, batch, tm.Hkv, self.capacity, tm.D), device=dev, dtype=BF16)
+        self.V = torch.zeros_like(self.K)
+        self.lens = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.lengths: List[int] = [0] * batch
+
+    def _set_lengths(self, lengths: Sequence[int]) -> None:
+        self.lengths = [int(n) for n in lengths]
+        self.lens.copy_(torch.tensor(self.lengths, dtype=torch.int32))
+
+    def truncate(self, lengths: Union[int, Sequence[int]]) -> None:
+        """Roll rows back to their first lengths[b] positions (an int applies to every row). Only shrinks: host arithmetic and one
+        small copy - the rows behind the new lengths stay in memory and are never read."""
+        want = [int(lengths)] * self.batch if isinstance(lengths, int) else [int(n) for n in lengths]
+        if len(want) != self.batch:
+            raise ValueError(f"KVCache.truncate: {len(want)} lengths for {self.batch} rows")
+        for b, (n, have) in enumerate(zip(want, self.lengths)):
+            if n < 0 or n > have:
+                raise ValueError(f"KVCache.truncate: row {b} holds {have} positions, cannot be set to {n} (truncate only shrinks)")
+        self._set_lengths(want)
+
+    def clone(self) -> "KVCache":
+        other = object.__new__(KVCache)
+        other.capacity, other.batch = self.capacity, self.batch
+        other.K, other.V, other.lens = self.K.clone(), self.V.clone(), self.lens.clone()
+        other.lengths = list(self.lengths)
+        return other
+
+
+def _plan_extend(spans: Sequence[Tuple[int, int]], cached: Sequence[int], capacity: int, max_new: int = 0) -> List[Tuple[int, int]]:
+    """Which columns of each row extend() computes: (first new column, count) per row, for attended runs `spans` (_row_spans) whose
+    first cached[b] positions are in the cache already. Host arithmetic only; raises before anything is launched: the cache's batch
+    is not the number of rows, a row has nothing new, or a row (+ max_new tokens to decode after it) would pass the capacity."""
+    if len(cached) != len(spans):
+        raise ValueError(f"kv_cache: the cache holds {len(cached)} rows, the call has {len(spans)}")
+    plan = []
+    for b, ((lo, n), have) in enumerate(zip(spans, cached)):
+        if n <= have:
+            raise ValueError(f"kv_cache: row {b} has {n} attended positions and {have} of them cached: nothing new to compute "
+                             "(pass each row's whole sequence so far; KVCache.truncate rolls a row back)")
+        if n + max_new > capacity:
+            raise ValueError(f"kv_cache: row {b} needs {n} + {max_new} positions, the cache's capacity is {capacity}")
+        plan.append((lo + have, n - have))
+    return plan
+
+
+def _extend_planned(tm, cache: KVCache, embeds: torch.Tensor, plan: Sequence[Tuple[int, int]]) -> torch.Tensor:
+    """Compute the planned columns of every row against the cache, append their K/V and advance the lengths. -> last hidden [B, H]."""
+    B, _, H = embeds.shape
+    counts = [n for _, n in plan]
+    chunk = torch.zeros((B, max(counts), H), device=embeds.device, dtype=BF16)
+    for b, (lo, n) in enumerate(plan):
+        chunk[b, :n] = embeds[b, lo:lo + n]
+    new_lens = torch.tensor(counts, dtype=torch.int32).to(embeds.device)
+    h_last = tm.forward_append(chunk, cache.K, cache.V, cache.lens, new_lens, counts)
+    cache.lens.add_(new_lens)
+    cache.lengths = [have + n for have, n in zip(cache.lengths, counts)]
+    return h_last
+
+
+@torch.no_grad()
+def extend(tm, cache: KVCache, inputs_embeds: Optional[torch.Tensor] = None, input_ids: Optional[torch.Tensor] = None,
+           attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformers' forward with `past_key_values`: the caller passes each row's WHOLE sequence so far (left or right padded, the
+    attended run found as generate() finds it); its first cache.lengths[b] positions are taken as cached and not looked at, the rest
+    is run through the model against the cache (tm.forward_append) and appended. Rows may differ in cached and new lengths; a row with
+    nothing new or one that would pass the capacity raises ValueError before any launch. Returns the last hidden state, bf16 [B, H]
+    (pre-final-norm: tm.logits_all turns it into logits). A prompt can go through in pieces: extend() the first part, then the whole."""
+    if (inputs_embeds is None) == (input_ids is None):
+        raise ValueError("pass exactly one of inputs_embeds / input_ids")
+    dev = tm.flat_w.device
+    shape_src = inputs_embeds if inputs_embeds is not None else input_ids
+    if attention_mask is None:
+        attention_mask = torch.ones(tuple(shape_src.shape[:2]), dtype=torch.int64)
+    plan = _plan_extend(_row_spans(attention_mask), cache.lengths, cache.capacity)
+    embeds = tm.get_input_embeddings()(input_ids.to(dev)) if input_ids is not None else inputs_embeds.to(dev, BF16)
+    return _extend_planned(tm, cache, embeds, plan)
+
+
 class DecodeState:
     """Device-resident state of one generate() call."""
 
-    def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0, sampling: bool = False):
+    def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0, sampling: bool = False,
+                 kv: Optional[KVCache] = None):
         c, dev = tm.config, tm.flat_w.device
         self.B, self.Lmax = B, Lmax
         nl = c.num_hidden_layers
-        self.K = torch.zeros((nl, B, tm.Hkv, Lmax, tm.D), device=dev, dtype=BF16)
-        self.V = torch.zeros((nl, B, tm.Hkv, Lmax, tm.D), device=dev, dtype=BF16)
-        self.lens = torch.zeros(B, device=dev, dtype=torch.int32)
+        if kv is not None:      # a session's cache: decode on its own K / V and lengths (Lmax is its capacity)
+            assert kv.batch == B and kv.capacity == Lmax
+            self.K, self.V, self.lens = kv.K, kv.V, kv.lens
+        else:
+            self.K = torch.zeros((nl, B, tm.Hkv, Lmax, tm.D), device=dev, dtype=BF16)
+            self.V = torch.zeros((nl, B, tm.Hkv, Lmax, tm.D), device=dev, dtype=BF16)
+            self.lens = torch.zeros(B, device=dev, dtype=torch.int32)
         self.step = torch.zeros(1, device=dev, dtype=torch.int32)
         self.finished = torch.zeros(B, device=dev, dtype=torch.int32)
         self.next_ids = torch.zeros(B, device=dev, dtype=torch.int32)
@@ -183,7 +287,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
              num_beams: int = 1, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
              use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False,
-             output_logprobs: bool = False, **unused):
+             output_logprobs: bool = False, kv_cache: Optional[KVCache] = None, **unused):
     """transformers `generate` for the greedy case. With `inputs_embeds` only the NEW tokens are returned (as
     transformers does); with `input_ids` the prompt is prepended and, like transformers, takes part in the repetition
     penalty and n-gram ban. Finished rows emit pad_token_id; generation stops when every row has produced eos or after
@@ -192,12 +296,17 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     columns), trimmed at the same stop column as the ids. An entry is the log-probability of the emitted id under the model's own
     distribution - log_softmax of the RAW logits, before the repetition penalty and the n-gram ban (transformers'
     compute_transition_scores on `output_logits`) - so with either processor on, an emitted id need not be the raw argmax. The step
-    that emits a row's eos carries that token's log-probability; every later (pad) step of the row is exactly 0.0."""
+    that emits a row's eos carries that token's log-probability; every later (pad) step of the row is exactly 0.0.
+    kv_cache=KVCache (transformers' `past_key_values`): pass each row's whole sequence so far; only what the cache does not hold yet is
+    computed (extend()), decoding runs on the cache's own K/V (Lmax = its capacity) and on return cache.lengths[b] counts the leading
+    positions of "attended prompt + emitted ids up to and including the first eos" whose K/V are cached: prompt_b + min(steps_run - 1,
+    index of the row's first eos + 1). The id picked last has no K/V yet - the next turn's extend() computes it with the new tokens.
+    A row longer than capacity - max_new_tokens raises ValueError before anything is launched."""
     if do_sample or num_beams != 1:
         raise NotImplementedError("generate() is greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use; "
                                   "sample() draws with temperature / top-k / top-p; beam_search() searches with num_beams beams")
     return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1)
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1, kv_cache)
 
 
 def _check_sample_args(temperature, top_k, top_p, num_return_sequences, n_prompts) -> None:
@@ -220,7 +329,7 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
            no_repeat_ngram_size: int = 0, eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
            use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False, output_logprobs: bool = False,
            temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
-           **unused):
+           kv_cache: Optional[KVCache] = None, **unused):
     """transformers `generate(do_sample=True)`: every keyword of generate() above with the same meaning (same processors, same
     eos / pad handling, same return values, output_logprobs included), the pick drawn instead of maximised (vq3_sample_pick, inside
     the captured step like the greedy pick). After the repetition penalty and the n-gram ban, with s = logit / temperature:
@@ -235,19 +344,22 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
     num_return_sequences = n draws n continuations of every prompt row: output row b * n + j is draw j of prompt b (transformers'
     order), B * n <= 8. Each prompt is prefilled once; its K/V rows and last hidden state are copied to its n cache rows.
     output_logprobs=True: an entry is log_softmax of the RAW logits at the sampled id (compute_transition_scores on `output_logits`),
-    not the probability the id was drawn with after the warpers."""
+    not the probability the id was drawn with after the warpers.
+    kv_cache: as in generate(); with a cache num_return_sequences must be 1 (the cache rows would have to be fanned out)."""
     shape_src = inputs_embeds if inputs_embeds is not None else input_ids
     _check_sample_args(temperature, top_k, top_p, num_return_sequences, 0 if shape_src is None else int(shape_src.shape[0]))
     if seed is None:
         seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
     sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
     return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, int(num_return_sequences))
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, int(num_return_sequences), kv_cache)
 
 
 def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-         pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, n_draws):
+         pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, n_draws, kv_cache=None):
     """The body of generate() (sampling None, n_draws 1) and sample(): prefill, one eager pick, then the decode steps."""
+    if kv_cache is not None and n_draws != 1:
+        raise ValueError("kv_cache: num_return_sequences must be 1 (fanning a cache row out to several draws is not implemented)")
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if max_new_tokens < 1:
@@ -264,6 +376,7 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
     if attention_mask is None:
         attention_mask = torch.ones((B, L0), device=dev, dtype=torch.int64)
     spans = _row_spans(attention_mask)
+    plan = None if kv_cache is None else _plan_extend(spans, kv_cache.lengths, kv_cache.capacity, max_new_tokens)
     B *= n_draws                                # output rows: n_draws per prompt row, prompt-major
     eos = None
     if eos_token_id is not None:
@@ -274,14 +387,17 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
     opts = dict(penalty=float(repetition_penalty), ngram=int(no_repeat_ngram_size), eos=eos,
                 pad=0 if pad_token_id is None else int(pad_token_id), sample=sampling)
     n_prompt = L0 if input_ids is not None else 0
-    Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64)
+    Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64) if kv_cache is None else kv_cache.capacity
     st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens, logprob_cols=max_new_tokens if output_logprobs else 0, prompt_cols=n_prompt,
-                     sampling=sampling is not None)
+                     sampling=sampling is not None, kv=kv_cache)
     if input_ids is not None:
         st.generated[:, :L0] = input_ids.repeat_interleave(n_draws, dim=0)
         st.step.fill_(L0)
     cos, sin = tm.rope(Lmax)
-    h_last = _prefill(tm, st, embeds, spans, n_draws)
+    if kv_cache is None:
+        h_last = _prefill(tm, st, embeds, spans, n_draws)
+    else:                                       # only what the cache does not hold; st.K / st.V / st.lens are the cache's own
+        h_last = _extend_planned(tm, kv_cache, embeds, plan)
     _logits_and_pick(tm, st, h_last, opts)
     ops.decode_advance(None, B, st.step)
     if use_graph is None:
@@ -343,10 +459,22 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
         first = torch.where(hit.any(1), hit.float().argmax(1), torch.full((B,), 1 << 30))
         if int(first.max()) < (1 << 30):
             stop = min(done_steps, int(first.max()) + 1)
+    if kv_cache is not None:
+        # every decode step cached the id picked before it: done_steps - 1 of them, valid up to and including the row's first eos
+        # (the pad steps of a finished row lie behind that and are overwritten by the next extend)
+        new = gen[:, n_prompt:]
+        kept = [done_steps - 1] * B
+        if eos is not None:
+            hit = torch.zeros_like(new, dtype=torch.bool)
+            for e in eos.tolist():
+                hit |= new == e
+            kept = [min(done_steps - 1, int(hit[b].float().argmax()) + 1) if bool(hit[b].any()) else done_steps - 1 for b in range(B)]
+        kv_cache._set_lengths([n + k for (_, n), k in zip(spans, kept)])
     out = gen[:, : n_prompt + stop].to(dev)
     ret = (out,) if st.logprobs is None else (out, st.logprobs[:, :stop].clone())
     if return_stats:
-        stats = {"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None}
+        stats = {"steps_run": done_steps, "graph": graph is not None, "Lmax": Lmax, "persistent": st.persistent is not None,
+                 "prefilled": [n for _, n in (spans if plan is None else plan)]}
         if sampling is not None:
             stats["seed"] = sampling["seed"]
         ret += (stats,)

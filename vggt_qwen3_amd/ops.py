@@ -766,6 +766,37 @@ def qwen_decode_attn(Q, Kc, Vc, lens, B, Hq, Hkv, D, Lmax, scale) -> torch.Tenso
     return O
 
 
+def qwen_append_qkprep(qkv, q_w, k_w, cos, sin, lens, new_lens, Kc, Vc, B, Ln, Hq, Hkv, D, Lmax, eps) -> torch.Tensor:
+    """A chunk of Ln tokens per row behind the cached prefix: token t of row b at position lens[b] + t; K / V into cache rows
+    lens[b] + t of Kc / Vc [B, Hkv, Lmax, D]; -> Q bf16 [B, Hq, Ln, D]. Tokens t >= new_lens[b] write nothing (their Q rows are 0)."""
+    _req(qkv, BF16, "append qkv"); _req(lens, torch.int32, "append lens"); _req(new_lens, torch.int32, "append new_lens")
+    _req(Kc, BF16, "K cache"); _req(Vc, BF16, "V cache"); _req(cos, BF16, "append cos"); _req(sin, BF16, "append sin")
+    assert qkv.is_contiguous() and qkv.shape == (B * Ln, (Hq + 2 * Hkv) * D)
+    assert Kc.is_contiguous() and Vc.is_contiguous() and Kc.shape == (B, Hkv, Lmax, D) and Vc.shape == Kc.shape
+    assert cos.shape[-2] >= Lmax and cos.shape[-1] == D and cos.is_contiguous() and sin.is_contiguous() and sin.shape == cos.shape
+    assert lens.numel() == B and new_lens.numel() == B and lens.is_contiguous() and new_lens.is_contiguous()
+    Q = torch.empty((B, Hq, Ln, D), device=qkv.device, dtype=BF16)
+    check(_lib.load().vq3_qwen_append_qkprep(qkv.data_ptr(), q_w.data_ptr(), k_w.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                                             lens.data_ptr(), new_lens.data_ptr(), Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), B, Ln,
+                                             Hq, Hkv, D, Lmax, eps, _stream()), "vq3_qwen_append_qkprep")
+    return Q
+
+
+def qwen_append_attn(Q, Kc, Vc, lens, new_lens, B, Ln, Hq, Hkv, D, Lmax, scale, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal GQA attention of a chunk against the cache: query t of row b over cache rows 0 .. lens[b] + t (lens before the chunk).
+    -> O bf16 [B*Ln, Hq*D] token-major; rows t >= new_lens[b] are exactly 0."""
+    _req(Q, BF16, "append Q"); _req(Kc, BF16, "K cache"); _req(Vc, BF16, "V cache")
+    _req(lens, torch.int32, "append lens"); _req(new_lens, torch.int32, "append new_lens")
+    assert Q.is_contiguous() and Q.shape == (B, Hq, Ln, D)
+    assert Kc.is_contiguous() and Vc.is_contiguous() and Kc.shape == (B, Hkv, Lmax, D) and Vc.shape == Kc.shape
+    assert lens.numel() == B and new_lens.numel() == B and lens.is_contiguous() and new_lens.is_contiguous()
+    O = _out2d(out, B * Ln, Hq * D, Q, "qwen_append_attn")
+    check(_lib.load().vq3_qwen_append_attn(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), lens.data_ptr(), new_lens.data_ptr(),
+                                           O.data_ptr(), B, Ln, Hq, Hkv, D, Lmax, O.stride(0), scale, _stream()),
+          "vq3_qwen_append_attn")
+    return O
+
+
 def greedy_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids, pad_id, next_ids, V) -> None:
     _req(logits, BF16, "pick logits"); _req(work, F32, "pick work"); _req(generated, torch.int64, "pick generated")
     _req(step, torch.int32, "pick step"); _req(finished, torch.int32, "pick finished"); _req(next_ids, torch.int32, "pick next")

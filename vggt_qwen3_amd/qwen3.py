@@ -19,7 +19,7 @@ import math
 import os
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -569,6 +569,71 @@ class Qwen3ForCausalLM(nn.Module):
         if wd_off is not None:
             out["wd_off"], out["wd_ticket"] = wd_off, self._wd_ticket
         return h, out
+
+    def forward_append(self, chunk: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, lens: torch.Tensor, new_lens: torch.Tensor,
+                       new_counts: Sequence[int]) -> torch.Tensor:
+        """forward_hidden(save=False) for a chunk of new positions behind a cached prefix (transformers' `past_key_values` path of
+        modeling_qwen3.py:237-280,294-323): chunk bf16 [B, Ln0, H] holds row b's new_counts[b] new embeddings at its front, at positions
+        lens[b] .. lens[b] + new_counts[b] - 1; Kc / Vc [layers, B, Hkv, Lmax, 128] are the caches, lens / new_lens i32 [B] on the device
+        (new_lens = new_counts). Same projections, norms, fused SwiGLU and LoRA hooks as forward_hidden; the attention is
+        vq3_qwen_append_qkprep (K / V of the chunk go straight into the caches) + vq3_qwen_append_attn. The chunk is padded to a
+        multiple of 8 as forward_hidden pads; tokens t >= new_lens[b] are padding: they write nothing to the cache and their attention
+        rows are 0. lens is NOT advanced here. Returns each row's hidden state at its last new position, bf16 [B, H] (pre-final-norm)."""
+        B, Ln0, H = chunk.shape
+        c = self.config
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        nl = c.num_hidden_layers
+        if D != 128 or Hq % Hkv or Hq // Hkv > 4:
+            raise NotImplementedError(f"forward_append: the cache attention takes head_dim 128 and 1..4 query heads per kv head, "
+                                      f"got head_dim {D}, {Hq} / {Hkv} heads")
+        if Kc.dim() != 5 or tuple(Kc.shape[:3]) != (nl, B, Hkv) or Kc.shape[4] != D or Vc.shape != Kc.shape:
+            raise ValueError(f"forward_append: caches must be [{nl}, {B}, {Hkv}, Lmax, {D}], got {tuple(Kc.shape)} / {tuple(Vc.shape)}")
+        if len(new_counts) != B or min(new_counts) < 1 or max(new_counts) > Ln0:
+            raise ValueError(f"forward_append: every row needs 1..{Ln0} new positions, got {list(new_counts)}")
+        Lmax = Kc.shape[3]
+        Ln = round_up(Ln0, 8)
+        if Ln != Ln0:
+            chunk = torch.cat([chunk, chunk.new_zeros((B, Ln - Ln0, H))], dim=1)
+        cos, sin = self.rope(Lmax)
+        h = chunk.reshape(B * Ln, H)
+        if self.lora_frozen:
+            self.lora.refresh_compute_copy()
+        f8 = getattr(self, "_fp8", None)
+        fuse = ops.swiglu_fwd_fusable(B * Ln, c.intermediate_size, H)
+        for i in range(nl):
+            xn1 = ops.rmsnorm_fwd(h, self._w[f"l{i}.ln1"], c.rms_norm_eps)
+            qkv = self._proj(xn1, f"l{i}.qkv")
+            if self.lora_frozen:
+                self.lora.fwd_qkv(i, xn1, qkv, False)
+            Q = ops.qwen_append_qkprep(qkv, self._w[f"l{i}.qn"], self._w[f"l{i}.kn"], cos, sin, lens, new_lens, Kc[i], Vc[i], B, Ln, Hq,
+                                       Hkv, D, Lmax, c.rms_norm_eps)
+            ao = ops.qwen_append_attn(Q, Kc[i], Vc[i], lens, new_lens, B, Ln, Hq, Hkv, D, Lmax, D ** -0.5)
+            h_mid = self._proj(ao, f"l{i}.o", residual=h)
+            if self.lora_frozen:
+                self.lora.fwd_o(i, ao, h_mid, False)
+            xn2 = ops.rmsnorm_fwd(h_mid, self._w[f"l{i}.ln2"], c.rms_norm_eps)
+            if f8 is None and fuse:
+                _, act = ops.gemm_swiglu_fwd(xn2, self._w[f"l{i}.gu"], keep_gu=False)
+            elif f8 is not None and fuse and H % 128 == 0:
+                wq, ws = f8[f"l{i}.gu"]
+                xq, xs = ops.quant_fp8_rows(xn2)
+                _, act = ops.gemm_fp8_ex(xq, xs, wq, ws, mode=1, keep_gu=False)
+            else:
+                act = ops.silu_mul_fwd(self._proj(xn2, f"l{i}.gu"))
+            h = self._proj(act, f"l{i}.down", residual=h_mid)
+        last = torch.tensor([b * Ln + n - 1 for b, n in enumerate(new_counts)], dtype=torch.int32).to(h.device)
+        return ops.gather_rows(h, last, B, B)
+
+    def kv_cache(self, batch: int, capacity: int):
+        """An empty KV cache for `batch` rows of up to `capacity` positions (vggt_qwen3_amd/generate.py: KVCache)."""
+        from .generate import KVCache
+        return KVCache(self, batch, capacity)
+
+    def extend(self, cache, *args, **kwargs):
+        """Run the uncached tail of every row through the model and append its K / V to `cache` (vggt_qwen3_amd/generate.py: extend)."""
+        from .generate import extend as _extend
+        self._pass_weights_gate()
+        return _extend(self, cache, *args, **kwargs)
 
     @staticmethod
     def label_rows(labels: torch.Tensor):
