@@ -391,6 +391,16 @@ int vq3_pack_tokens(const int32_t* prompt_ids, const int32_t* prompt_off, const 
 int vq3_skinny_gemm_bf16(const void* x, const void* W, void* y, const void* residual, const void* ln_w, float eps,
                          int32_t xmode, int32_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy,
                          int64_t ldr, int32_t out_f32, void* stream);
+/* The same product for 1 <= M <= 64 on the matrix cores (csrc/decode_gemm.hip): nn.Linear for one token per row of a batch of up to
+ * 64 sequences, the weights streamed once. Arguments, xmode, stride and alignment rules, output types and rounding points are those
+ * of vq3_skinny_gemm_bf16; the fp32 sums are taken in another order. A shape that does not fill the chip with 64-row workgroups is
+ * cut into K slices that meet in `workspace`: vq3_decode_gemm_workspace_bytes(M, N, K) bytes of device memory (0: none needed, the
+ * pointer may be null), 16-byte aligned, uninitialised, owned by the caller and free again when the call's work on `stream` is done.
+ * The slices are added in a fixed order: the same arguments give the same bits on every call. */
+int vq3_decode_gemm_bf16(const void* x, const void* W, void* y, const void* residual, const void* ln_w, float eps,
+                         int32_t xmode, int32_t M, int32_t N, int32_t K, int64_t ldx, int64_t ldw, int64_t ldy,
+                         int64_t ldr, int32_t out_f32, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t vq3_decode_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K);
 /* The same product with e4m3 weights (config C5): Wq uint8 e4m3 [N, K] with one f32 scale per output row; the prepared
  * activation row f(x) is quantised per token in registers exactly as vq3_quant_fp8_rows does, so decode and the fp8
  * GEMM share one numeric contract. M <= 2, K % 16 == 0, K <= 12288; y bf16. */

@@ -123,6 +123,8 @@ SIGNATURES = {
     "vq3_resample_plan": [i32, i32, c_p, c_p],
     "vq3_resize_crop_u8": [c_p, i32, c_p, c_p, c_p, i32, i32, i32, c_p],
     "vq3_skinny_gemm_bf16": [c_p, c_p, c_p, c_p, c_p, f32, i32, i32, i32, i32, i64, i64, i64, i64, i32, c_p],
+    "vq3_decode_gemm_bf16": [c_p, c_p, c_p, c_p, c_p, f32, i32, i32, i32, i32, i64, i64, i64, i64, i32, c_p, i64, c_p],
+    "vq3_decode_gemm_workspace_bytes": [i32, i32, i32],
     "vq3_skinny_gemm_fp8": [c_p, c_p, c_p, c_p, c_p, c_p, f32, i32, i32, i32, i32, i64, i64, i64, i64, c_p],
     "vq3_qwen_decode_qkprep": [c_p] * 9 + [i32, i32, i32, i32, i32, f32, c_p],
     "vq3_qwen_decode_attn": [c_p] * 5 + [i32, i32, i32, i32, i32, f32, c_p],
@@ -165,7 +167,8 @@ SIGNATURES = {
     "vq3_lora_up_add": [c_p, i64, i32, c_p, i64, C.POINTER(LoraTarget), i32, i32, f32, f32, C.c_uint64, i64, c_p],
     "vq3_lora_wgrad_part": [c_p, i64, c_p, i64, i32, C.POINTER(LoraTarget), i32, i32, f32, f32, C.c_uint64, i64, c_p, i64, c_p],
 }
-_RESTYPES = {"vq3_last_error": C.c_char_p, "vq3_target_arch": C.c_char_p, "vq3_qwen_decode_layers_workspace_bytes": i64}
+_RESTYPES = {"vq3_last_error": C.c_char_p, "vq3_target_arch": C.c_char_p, "vq3_qwen_decode_layers_workspace_bytes": i64,
+             "vq3_decode_gemm_workspace_bytes": i64}
 
 _lib = None
 

@@ -9,7 +9,7 @@ arkit_inference.py:274-284) plus the vision-token INSERTION splice those scripts
 Design (MI355X): prompts are prefilled without their padding (left-padded rows are compacted, so no pad token is ever
 computed and positions are 0..n-1 exactly as transformers derives them from the mask); K/V live in one
 [layers, B, Hkv, Lmax, 128] bf16 buffer per operand; a decode step streams every weight once through the skinny
-GEMM; all step state is in device memory, so the whole step is captured once in a HIP graph and replayed per token -
+GEMM (up to 8 rows, FMA) or the decode GEMM (9 to 64 rows with max_rows=, MFMA: csrc/decode_gemm.hip); all step state is in device memory, so the whole step is captured once in a HIP graph and replayed per token -
 the host only checks the `finished` flags every few steps. One row at Qwen3-4B's shape (the reference's case): the 36
 layers of a step are ONE persistent launch (csrc/decode_layers.hip) + lm_head + pick; otherwise ~220 launches.
 
@@ -225,7 +225,7 @@ def _prefill(tm, st: DecodeState, embeds: torch.Tensor, spans: Sequence[Tuple[in
 
 def _logits_and_pick(tm, st: DecodeState, h: torch.Tensor, opts) -> None:
     c = tm.config
-    logits = ops.skinny_linear(h, tm._w["embed"], n=tm.vocab, ln_w=tm._w["norm"], eps=c.rms_norm_eps)
+    logits = ops.decode_linear(h, tm._w["embed"], n=tm.vocab, ln_w=tm._w["norm"], eps=c.rms_norm_eps)
     sm, bm = opts.get("sample"), opts.get("beam")
     if bm is not None:              # beam search: the beam step in the pick's place, then the cache rows follow the surviving beams
         bs = bm["state"]
@@ -262,7 +262,7 @@ def _decode_step(tm, st: DecodeState, cos, sin, opts) -> None:
         if f8 is not None:
             wq, ws = f8[name]
             return ops.skinny_linear_fp8(x, wq, ws, **kw)
-        return ops.skinny_linear(x, tm._w[name], **kw)
+        return ops.decode_linear(x, tm._w[name], **kw)       # <= 8 rows: the FMA skinny GEMM; 9..64: the MFMA decode GEMM
 
     lo = tm.lora if tm.lora_frozen else None                        # unmerged LoRA adapters: their terms after q|k|v and o
     for i in range(c.num_hidden_layers):
@@ -287,7 +287,7 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
              num_beams: int = 1, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
              use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False,
-             output_logprobs: bool = False, kv_cache: Optional[KVCache] = None, **unused):
+             output_logprobs: bool = False, kv_cache: Optional[KVCache] = None, max_rows: int = 8, **unused):
     """transformers `generate` for the greedy case. With `inputs_embeds` only the NEW tokens are returned (as
     transformers does); with `input_ids` the prompt is prepended and, like transformers, takes part in the repetition
     penalty and n-gram ban. Finished rows emit pad_token_id; generation stops when every row has produced eos or after
@@ -301,7 +301,13 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     computed (extend()), decoding runs on the cache's own K/V (Lmax = its capacity) and on return cache.lengths[b] counts the leading
     positions of "attended prompt + emitted ids up to and including the first eos" whose K/V are cached: prompt_b + min(steps_run - 1,
     index of the row's first eos + 1). The id picked last has no K/V yet - the next turn's extend() computes it with the new tokens.
-    A row longer than capacity - max_new_tokens raises ValueError before anything is launched."""
+    A row longer than capacity - max_new_tokens raises ValueError before anything is launched.
+    max_rows: the caller's cap on the rows decoded per call, 1..64 (ops.DECODE_MAX_ROWS); more rows than that raise ValueError before
+    the GPU is touched. Up to 8 rows a step runs the FMA skinny GEMMs whatever max_rows says; 9..64 rows (bf16 weights, frozen LoRA
+    adapters included) run one MFMA weight-streaming GEMM per projection, so a step still streams every weight once. With kv_cache
+    the cache's batch is the row count."""
+    shape_src = inputs_embeds if inputs_embeds is not None else input_ids
+    _check_rows("generate", max_rows, 0 if shape_src is None else int(shape_src.shape[0]))
     if do_sample or num_beams != 1:
         raise NotImplementedError("generate() is greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use; "
                                   "sample() draws with temperature / top-k / top-p; beam_search() searches with num_beams beams")
@@ -309,7 +315,16 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
                 pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1, kv_cache)
 
 
-def _check_sample_args(temperature, top_k, top_p, num_return_sequences, n_prompts) -> None:
+def _check_rows(who: str, max_rows, n_prompts: int, n_draws: int = 1) -> None:
+    """max_rows itself, then the output rows (prompts x draws) against it; host arithmetic only."""
+    if isinstance(max_rows, bool) or int(max_rows) != max_rows or not (1 <= max_rows <= ops.DECODE_MAX_ROWS):
+        raise ValueError(f"{who}: max_rows must be an integer in 1..{ops.DECODE_MAX_ROWS}, got {max_rows}")
+    if n_prompts * n_draws > max_rows:
+        raise ValueError(f"{who}: at most {max_rows} rows per call (max_rows=, up to {ops.DECODE_MAX_ROWS}), got {n_prompts} prompts x "
+                         f"{n_draws} draws")
+
+
+def _check_sample_args(temperature, top_k, top_p, num_return_sequences, n_prompts, max_rows=8) -> None:
     """sample()'s own arguments; host arithmetic only."""
     if not (temperature > 0 and temperature < float("inf")):
         raise ValueError(f"sample: temperature must be > 0 and finite, got {temperature}")
@@ -319,8 +334,7 @@ def _check_sample_args(temperature, top_k, top_p, num_return_sequences, n_prompt
         raise ValueError(f"sample: top_p must be in (0, 1], got {top_p}")
     if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
         raise ValueError(f"sample: num_return_sequences must be an integer >= 1, got {num_return_sequences}")
-    if n_prompts * num_return_sequences > 8:
-        raise ValueError(f"sample: at most 8 rows per call (skinny GEMM width), got {n_prompts} prompts x {num_return_sequences} draws")
+    _check_rows("sample", max_rows, n_prompts, int(num_return_sequences))
 
 
 @torch.no_grad()
@@ -329,7 +343,7 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
            no_repeat_ngram_size: int = 0, eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
            use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False, output_logprobs: bool = False,
            temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
-           kv_cache: Optional[KVCache] = None, **unused):
+           kv_cache: Optional[KVCache] = None, max_rows: int = 8, **unused):
     """transformers `generate(do_sample=True)`: every keyword of generate() above with the same meaning (same processors, same
     eos / pad handling, same return values, output_logprobs included), the pick drawn instead of maximised (vq3_sample_pick, inside
     the captured step like the greedy pick). After the repetition penalty and the n-gram ban, with s = logit / temperature:
@@ -342,12 +356,13 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
     HIP graph, on either step route. seed=None takes a 64-bit seed from torch's default CPU generator (torch.manual_seed governs it);
     return_stats reports the seed used.
     num_return_sequences = n draws n continuations of every prompt row: output row b * n + j is draw j of prompt b (transformers'
-    order), B * n <= 8. Each prompt is prefilled once; its K/V rows and last hidden state are copied to its n cache rows.
+    order), B * n <= max_rows (8 unless the caller raises it, up to 64: see generate()). Each prompt is prefilled once; its K/V rows and
+    last hidden state are copied to its n cache rows.
     output_logprobs=True: an entry is log_softmax of the RAW logits at the sampled id (compute_transition_scores on `output_logits`),
     not the probability the id was drawn with after the warpers.
     kv_cache: as in generate(); with a cache num_return_sequences must be 1 (the cache rows would have to be fanned out)."""
     shape_src = inputs_embeds if inputs_embeds is not None else input_ids
-    _check_sample_args(temperature, top_k, top_p, num_return_sequences, 0 if shape_src is None else int(shape_src.shape[0]))
+    _check_sample_args(temperature, top_k, top_p, num_return_sequences, 0 if shape_src is None else int(shape_src.shape[0]), max_rows)
     if seed is None:
         seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
     sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
@@ -370,9 +385,7 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
         embeds = tm.get_input_embeddings()(input_ids)
     else:
         embeds = inputs_embeds.to(dev, BF16)
-    B, L0, H = embeds.shape
-    if B > 8:
-        raise ValueError("generate: at most 8 rows per call (skinny GEMM width)")
+    B, L0, H = embeds.shape                     # (generate() / sample() have checked the rows against max_rows)
     if attention_mask is None:
         attention_mask = torch.ones((B, L0), device=dev, dtype=torch.int64)
     spans = _row_spans(attention_mask)

@@ -746,6 +746,40 @@ def skinny_linear(x: torch.Tensor, w: torch.Tensor, *, residual: Optional[torch.
     return out
 
 
+SKINNY_MAX_ROWS = 8      # vq3_skinny_gemm_bf16 (FMA, acc[R][MT] per lane)
+DECODE_MAX_ROWS = 64     # vq3_decode_gemm_bf16 (MFMA, four 16-row batch tiles); vq3_decode_advance checks the same bound
+
+
+def decode_linear(x: torch.Tensor, w: torch.Tensor, *, residual: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None, out_dtype=BF16, ln_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                  swiglu: bool = False) -> torch.Tensor:
+    """skinny_linear for 1..64 rows, same keywords: up to 8 rows ARE skinny_linear (the same call, the same bits); 9..64 rows stream
+    the weight once through the MFMA kernel (vq3_decode_gemm_bf16). Its K-slice workspace, where the shape needs one, is allocated
+    per call like the output: under graph capture it comes from the graph's own pool."""
+    M = x.shape[0]
+    if M <= SKINNY_MAX_ROWS:
+        return skinny_linear(x, w, residual=residual, n=n, out=out, out_dtype=out_dtype, ln_w=ln_w, eps=eps, swiglu=swiglu)
+    if M > DECODE_MAX_ROWS:
+        raise ValueError(f"decode_linear: at most {DECODE_MAX_ROWS} rows, got {M} (ops.linear is the GEMM for more)")
+    _req(x, BF16, "decode x"); _req(w, BF16, "decode w")
+    assert x.dim() == 2 and w.dim() == 2 and x.is_contiguous() and w.is_contiguous()
+    assert not (swiglu and ln_w is not None)
+    K = w.shape[1]
+    assert x.shape[1] == (2 * K if swiglu else K)
+    N = w.shape[0] if n is None else n
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=out_dtype)
+    if residual is not None:
+        _req(residual, BF16, "decode residual"); assert residual.shape == (M, N) and residual.is_contiguous()
+    xmode = 2 if swiglu else (1 if ln_w is not None else 0)
+    lib = _lib.load()
+    nbytes = int(lib.vq3_decode_gemm_workspace_bytes(M, N, K))
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes > 0 else None
+    check(lib.vq3_decode_gemm_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), _p(residual), _p(ln_w), eps, xmode, M, N, K, x.shape[1],
+                                   K, out.stride(0), N, 1 if out.dtype == F32 else 0, _p(ws), nbytes, _stream()), "vq3_decode_gemm_bf16")
+    return out
+
+
 def qwen_decode_qkprep(qkv, q_w, k_w, cos, sin, lens, Kc, Vc, B, Hq, Hkv, D, Lmax, eps) -> torch.Tensor:
     _req(qkv, BF16, "decode qkv"); _req(lens, torch.int32, "decode lens"); _req(Kc, BF16, "K cache"); _req(Vc, BF16, "V cache")
     assert qkv.is_contiguous() and qkv.shape == (B, (Hq + 2 * Hkv) * D)
