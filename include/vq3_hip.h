@@ -462,6 +462,34 @@ int vq3_sample_pick(const void* logits_bf16, int64_t ld_logits, float* work, int
                     int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty, int32_t no_repeat_ngram,
                     const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids, float temperature, int32_t top_k,
                     float top_p, uint64_t seed, void* sample_work, int32_t* n_kept, float* min_kept, void* stream);
+/* Decoding constraints for the two picks (replaces SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor,
+ * MinNewTokensLengthLogitsProcessor, PrefixConstrainedLogitsProcessor with a fixed allowed set, and one-token NoBadWordsLogitsProcessor
+ * entries): `planes` is device memory, three bit planes of `words` uint32 each, words * 32 >= V, bit (id & 31) of word id >> 5, shared
+ * by all rows. With n_new = *step - prompt_cols, read on the device at every call (so the call sits in a captured graph and gates
+ * itself), id is MASKED iff its bit is set in plane 0 (always: suppressed ids, the complement of an allowed set), or in plane 1 and
+ * n_new < min_new (the eos ids), or in plane 2 and n_new == 0 (begin-suppressed ids). Bits of ids >= V are never looked at. A masked id
+ * scores -inf exactly as an n-gram-banned id does: see each entry. The planes are only read. */
+typedef struct vq3_pick_mask {
+  const uint32_t* planes;
+  int32_t words, min_new, prompt_cols;
+} vq3_pick_mask;
+/* vq3_greedy_pick under a vq3_pick_mask: a masked id is never picked (a penalised id that is masked is -inf, not its rescaled value); a
+ * row with every id masked or banned picks id 0. Same state, same work, same bookkeeping (finished rows still emit pad_id: pad does not
+ * go through the logits), same tie rule, no rewrite of the logits: the mask is applied in the slice walk that streams the row, from
+ * the slice's words staged once per workgroup. V <= 520 192. */
+int vq3_greedy_pick_masked(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
+                           int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
+                           int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
+                           const vq3_pick_mask* mask, void* stream);
+/* vq3_sample_pick under a vq3_pick_mask: a masked id has z = -inf - it is not counted in the histogram (no mass in the top-k / top-p
+ * cuts, not in n_kept / min_kept), never kept and never drawn; a penalised id that is masked does not enter the cuts as a finite value.
+ * The draw of an unmasked id uses the same Philox counter as without a mask. sample_work is left zero as vq3_sample_pick leaves it: the
+ * two entries may alternate on one workspace. V <= 520 192. */
+int vq3_sample_pick_masked(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
+                           int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty, int32_t no_repeat_ngram,
+                           const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids, float temperature, int32_t top_k,
+                           float top_p, uint64_t seed, void* sample_work, int32_t* n_kept, float* min_kept, const vq3_pick_mask* mask,
+                           void* stream);
 /* lens[b] += 1 for b < B (B <= 64), *step += 1 (either pointer may be NULL): the last launch of a decode step. */
 int vq3_decode_advance(int32_t* lens, int32_t B, int32_t* step, void* stream);
 /* Per-token log-probabilities of bf16 logits [n, ld] with V valid columns (replaces transformers `output_logits` / the forward's

@@ -1,6 +1,7 @@
 """Decode throughput of Qwen3-4B (random weights) through text_model.generate(): tokens/s and the fraction of HBM
-bandwidth the weight stream achieves. Usage: python tools/bench_decode.py [--batch 1] [--prompt 200] [--new 64] [--logprobs]
-(--logprobs: generate(output_logprobs=True), the per-token log-probability kernel in every step)"""
+bandwidth the weight stream achieves. Usage: python tools/bench_decode.py [--batch 1] [--prompt 200] [--new 64] [--logprobs] [--constrain]
+(--logprobs: generate(output_logprobs=True), the per-token log-probability kernel in every step; --constrain: 16 suppress_tokens and
+min_new_tokens = 2 under an eos id, finished flags never polled: the masked greedy pick in every step and nothing else changed)"""
 import argparse
 import json
 import sys
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--layers", type=int, default=36)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--logprobs", action="store_true", help="generate(output_logprobs=True)")
+    ap.add_argument("--constrain", action="store_true", help="generate(suppress_tokens=16 ids, min_new_tokens=2, eos_token_id=)")
     a = ap.parse_args()
     cfg = Qwen3Config.qwen3_4b()
     cfg.num_hidden_layers = a.layers
@@ -32,6 +34,8 @@ def main():
               use_graph=not a.no_graph)
     if a.logprobs:
         kw["output_logprobs"] = True
+    if a.constrain:     # (min_new_tokens is capped by the shortest run below)
+        kw.update(suppress_tokens=list(range(1000, 1016)), min_new_tokens=2, eos_token_id=cfg.vocab_size - 1, check_every=1 << 30)
     tm.generate(max_new_tokens=4, **kw)                       # warm-up (library load, allocator)
     torch.cuda.synchronize()
     t0 = time.perf_counter(); tm.generate(max_new_tokens=2, **kw); torch.cuda.synchronize(); t_short = time.perf_counter() - t0
@@ -40,6 +44,7 @@ def main():
     per_tok = (t_long - t_short) / (a.new - 2)
     wbytes = 2 * sum(p.numel() for n, p in tm.named_parameters() if n != "lm_head.weight")   # every weight once (embedding = lm_head)
     print(json.dumps({"batch": a.batch, "prompt": a.prompt, "new_tokens": int(out.shape[1]), "graph": not a.no_graph, "logprobs": a.logprobs,
+                      "constrain": a.constrain,
                       "persistent_layers_kernel": stats["persistent"], "ms_per_token": per_tok * 1e3, "tokens_per_s": a.batch / per_tok,
                       "prefill_plus_2_ms": t_short * 1e3, "weight_GB_per_token": wbytes / 1e9,
                       "weight_stream_GBps": wbytes / per_tok / 1e9, "hbm_peak_GBps": 8000,

@@ -62,6 +62,10 @@ class BeamStepDesc(C.Structure):
                 ("repetition_penalty", f32), ("length_penalty", f32)]
 
 
+class PickMask(C.Structure):
+    _fields_ = [("planes", c_p), ("words", i32), ("min_new", i32), ("prompt_cols", i32)]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("part", c_p), ("out_bf16", c_p), ("nrows", i32), ("cols", i32), ("accumulate", i32)]
 
@@ -133,6 +137,9 @@ SIGNATURES = {
     "vq3_greedy_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, c_p],
     "vq3_sample_pick": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, f32, i32, f32, C.c_uint64, c_p, c_p,
                         c_p, c_p],
+    "vq3_greedy_pick_masked": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, C.POINTER(PickMask), c_p],
+    "vq3_sample_pick_masked": [c_p, i64, c_p, i32, i32, c_p, i32, c_p, c_p, f32, i32, c_p, i32, i64, c_p, f32, i32, f32, C.c_uint64, c_p,
+                               c_p, c_p, C.POINTER(PickMask), c_p],
     "vq3_decode_advance": [c_p, i32, c_p, c_p],
     "vq3_token_logprob": [c_p, i64, i32, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p],
     "vq3_token_logprob_step": [c_p, i64, i32, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p],

@@ -146,11 +146,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const bf16_t* __restri
 constexpr int PICK_NCH = 64;
 constexpr int PICK_OVL = 1024;  // overlay capacity per vocabulary slice: <= 512 penalised + <= 512 banned entries
 
-__global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
-                                                                  const int64_t* __restrict__ gen, int max_new,
-                                                                  const int32_t* __restrict__ step_p, float penalty,
-                                                                  int ngram, float* __restrict__ pval,
-                                                                  int32_t* __restrict__ pidx, int32_t* __restrict__ overflow) {
+// MASKED: the constraint planes of pick.h, staged for the slice in mw - a masked id is -inf wherever the walk or the penalty meets it
+template <bool MASKED>
+__device__ __forceinline__ void greedy_pick_partial_body(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                         const int64_t* __restrict__ gen, int max_new,
+                                                         const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                         float* __restrict__ pval, int32_t* __restrict__ pidx,
+                                                         int32_t* __restrict__ overflow, const vq3pick::MaskArgs& m, uint32_t* mw) {
   __shared__ int ov_id[PICK_OVL];
   __shared__ float ov_val[PICK_OVL];
   __shared__ int ov_n;
@@ -163,6 +165,7 @@ __global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* 
   const bf16_t* lg = logits + (long)b * ldl;
   const int64_t* g = gen + (long)b * max_new;
   if (tid == 0) ov_n = 0;
+  if constexpr (MASKED) vq3pick::mask_stage(m, step - m.prompt_cols, c0, c1, mw);
   __syncthreads();
   // penalty: distinct generated ids in this slice (first occurrence only: gather - rescale - scatter semantics)
   if (penalty != 1.0f) {
@@ -172,9 +175,13 @@ __global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* 
       bool first = true;
       for (int j = 0; j < i; ++j) first &= (g[j] != t);
       if (!first) continue;
-      const float sv = bf2f(lg[t]);
+      float sv = bf2f(lg[t]);
+      sv = sv < 0.f ? sv * penalty : sv / penalty;
+      if constexpr (MASKED) {
+        if (vq3pick::mask_bit(mw, c0, (int)t)) sv = -INFINITY;
+      }
       const int at = atomicAdd(&ov_n, 1);
-      if (at < PICK_OVL) { ov_id[at] = (int)t; ov_val[at] = sv < 0.f ? sv * penalty : sv / penalty; }
+      if (at < PICK_OVL) { ov_id[at] = (int)t; ov_val[at] = sv; }
     }
   }
   __syncthreads();
@@ -209,6 +216,9 @@ __global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* 
     float v = bf2f(lg[i]);
     for (int k = 0; k < n_ov; ++k)
       if (ov_id[k] == i) v = ov_val[k];       // duplicates of a banned id all hold -inf; penalised ids are unique
+    if constexpr (MASKED) {
+      if (vq3pick::mask_bit(mw, c0, i)) v = -INFINITY;
+    }
     if (v > best) { best = v; bi = i; }
   }
 #pragma unroll
@@ -225,6 +235,24 @@ __global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* 
     pval[b * PICK_NCH + c] = best;
     pidx[b * PICK_NCH + c] = bi;
   }
+}
+
+__global__ __launch_bounds__(256) void greedy_pick_partial_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                                  const int64_t* __restrict__ gen, int max_new,
+                                                                  const int32_t* __restrict__ step_p, float penalty,
+                                                                  int ngram, float* __restrict__ pval,
+                                                                  int32_t* __restrict__ pidx, int32_t* __restrict__ overflow) {
+  greedy_pick_partial_body<false>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, pval, pidx, overflow, vq3pick::MaskArgs{}, nullptr);
+}
+
+__global__ __launch_bounds__(256) void greedy_pick_partial_masked_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                                         const int64_t* __restrict__ gen, int max_new,
+                                                                         const int32_t* __restrict__ step_p, float penalty,
+                                                                         int ngram, float* __restrict__ pval,
+                                                                         int32_t* __restrict__ pidx, int32_t* __restrict__ overflow,
+                                                                         vq3pick::MaskArgs m) {
+  __shared__ uint32_t mw[vq3pick::MASK_SLICE_WORDS];
+  greedy_pick_partial_body<true>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, pval, pidx, overflow, m, mw);
 }
 
 __global__ __launch_bounds__(64) void greedy_pick_final_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
@@ -306,6 +334,32 @@ extern "C" int vq3_greedy_pick(const void* logits_bf16, int64_t ld_logits, float
   hipLaunchKernelGGL(greedy_pick_final_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pval, pidx, generated, max_new,
                      step, finished, eos_ids, n_eos, (long)pad_id, next_ids);
   VQ3_CHECK_LAUNCH("greedy_pick");
+  return 0;
+}
+
+extern "C" int vq3_greedy_pick_masked(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V,
+                                      int64_t* generated, int32_t max_new, const int32_t* step, int32_t* finished,
+                                      float repetition_penalty, int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos,
+                                      int64_t pad_id, int32_t* next_ids, const vq3_pick_mask* mask, void* stream) {
+  VQ3_CHECK_ARG(logits_bf16 && work && generated && step && finished && next_ids && mask, "greedy_pick_masked: null pointer");
+  VQ3_CHECK_ARG(B > 0 && V > 0 && max_new > 0 && ld_logits >= V, "greedy_pick_masked: bad shape");
+  VQ3_CHECK_ARG(max_new <= PICK_OVL / 2, "greedy_pick_masked: at most %d ids per row (prompt + new), got %d", PICK_OVL / 2, max_new);
+  VQ3_CHECK_ARG(repetition_penalty > 0.f, "greedy_pick_masked: repetition_penalty must be > 0, got %f", (double)repetition_penalty);
+  VQ3_CHECK_ARG(no_repeat_ngram >= 0 && n_eos >= 0 && (n_eos == 0 || eos_ids), "greedy_pick_masked: bad ngram / eos arguments");
+  const char* bad = vq3pick::mask_args_error(mask->planes, mask->words, mask->min_new, mask->prompt_cols, V);
+  VQ3_CHECK_ARG(bad == nullptr, "greedy_pick_masked: %s", bad);
+  VQ3_CHECK_ARG((V + PICK_NCH - 1) / PICK_NCH <= (vq3pick::MASK_SLICE_WORDS - 2) * 32, "greedy_pick_masked: V %d exceeds %d", V,
+                PICK_NCH * (vq3pick::MASK_SLICE_WORDS - 2) * 32);
+  float* pval = work;                     // work as in vq3_greedy_pick
+  int32_t* pidx = (int32_t*)(work + (long)B * PICK_NCH);
+  int32_t* overflow = pidx + (long)B * PICK_NCH;
+  const vq3pick::MaskArgs m{mask->planes, mask->words, mask->min_new, mask->prompt_cols};
+  hipLaunchKernelGGL(greedy_pick_partial_masked_kernel, dim3(PICK_NCH, B), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)logits_bf16, (long)ld_logits, V, generated, max_new, step, repetition_penalty,
+                     no_repeat_ngram, pval, pidx, overflow, m);
+  hipLaunchKernelGGL(greedy_pick_final_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pval, pidx, generated, max_new,
+                     step, finished, eos_ids, n_eos, (long)pad_id, next_ids);
+  VQ3_CHECK_LAUNCH("greedy_pick_masked");
   return 0;
 }
 

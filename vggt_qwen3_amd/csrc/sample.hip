@@ -47,8 +47,13 @@ __device__ __forceinline__ float bound_of_key(int k) { return k > 0xff80 ? INFIN
 // (greedy_pick_partial_kernel): entries [0, n_pen) are the distinct penalised ids (first occurrence; value < 0 ? value * penalty :
 // value / penalty), overwritten by -inf where the n-gram ban also hits; entries [n_pen, n_ov) are banned ids that were not penalised.
 // Every thread of the block calls it; returns false (block-uniform) on overflow, which max_new <= 512 rules out.
+// masked(id): the constraint planes' verdict on an id of [c0, c1) - a penalised id that is masked enters as -inf, never as a finite value.
+struct NoMask {
+  __device__ __forceinline__ bool operator()(int) const { return false; }
+};
+template <class MF>
 __device__ bool build_overlay(const bf16_t* __restrict__ lg, const int64_t* __restrict__ g, int n, int c0, int c1, float penalty,
-                              int ngram, int* ov_id, float* ov_val, int* ov_n, int& n_pen, int& n_ov) {
+                              int ngram, int* ov_id, float* ov_val, int* ov_n, int& n_pen, int& n_ov, MF masked) {
   const int tid = threadIdx.x, nt = blockDim.x;
   if (tid == 0) *ov_n = 0;
   __syncthreads();
@@ -61,7 +66,7 @@ __device__ bool build_overlay(const bf16_t* __restrict__ lg, const int64_t* __re
       if (!first) continue;
       const float sv = bf2f(lg[t]);
       const int at = atomicAdd(ov_n, 1);
-      if (at < OVL) { ov_id[at] = (int)t; ov_val[at] = sv < 0.f ? sv * penalty : sv / penalty; }
+      if (at < OVL) { ov_id[at] = (int)t; ov_val[at] = masked((int)t) ? -INFINITY : (sv < 0.f ? sv * penalty : sv / penalty); }
     }
   }
   __syncthreads();
@@ -89,10 +94,25 @@ __device__ bool build_overlay(const bf16_t* __restrict__ lg, const int64_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------ phase 1: histogram
-__global__ __launch_bounds__(256) void sample_hist_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
-                                                          const int64_t* __restrict__ gen, int max_new,
-                                                          const int32_t* __restrict__ step_p, float penalty, int ngram,
-                                                          int32_t* __restrict__ ws, int32_t* __restrict__ overflow) {
+// the verdict of a slice's staged words (pick.h), for the kernels that stream a slice
+struct SliceMask {
+  const uint32_t* mw;
+  int c0;
+  __device__ __forceinline__ bool operator()(int i) const { return vq3pick::mask_bit(mw, c0, i); }
+};
+// the same from the planes themselves, for the few changed ids the walk meets anywhere in the row
+struct RowMask {
+  vq3pick::MaskArgs m;
+  int n_new;
+  __device__ __forceinline__ bool operator()(int i) const { return (vq3pick::mask_word(m, i >> 5, n_new) >> (i & 31)) & 1u; }
+};
+
+// MASKED (here and in the draw): a masked id is not counted, so it carries no mass in either cut; mw is the slice's stage
+template <bool MASKED>
+__device__ __forceinline__ void sample_hist_body(const bf16_t* __restrict__ logits, long ldl, int V, const int64_t* __restrict__ gen,
+                                                 int max_new, const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                 int32_t* __restrict__ ws, int32_t* __restrict__ overflow, const vq3pick::MaskArgs& m,
+                                                 uint32_t* mw) {
   __shared__ int ov_id[OVL];
   __shared__ float ov_val[OVL];
   __shared__ int ov_n;
@@ -102,7 +122,14 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(const bf16_t* __restri
   const int c0 = min(V, c * per), c1 = min(V, c0 + per);
   const bf16_t* lg = logits + (long)b * ldl;
   int n_pen, n_ov;
-  if (!build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov)) {
+  bool fits;
+  if constexpr (MASKED) {
+    vq3pick::mask_stage(m, *step_p - m.prompt_cols, c0, c1, mw);     // (build_overlay syncs before it reads)
+    fits = build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov, SliceMask{mw, c0});
+  } else {
+    fits = build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov, NoMask{});
+  }
+  if (!fits) {
     if (tid == 0) atomicExch(overflow, 1);
     return;
   }
@@ -110,9 +137,26 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(const bf16_t* __restri
   for (int i = c0 + tid; i < c1; i += 256) {
     bool changed = false;
     for (int k = 0; k < n_ov; ++k) changed |= (ov_id[k] == i);
+    if constexpr (MASKED) changed |= vq3pick::mask_bit(mw, c0, i);
     const int key = key_of(lg[i]);
     if (!changed && key >= 0) atomicAdd(hist + key, 1);
   }
+}
+
+__global__ __launch_bounds__(256) void sample_hist_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                          const int64_t* __restrict__ gen, int max_new,
+                                                          const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                          int32_t* __restrict__ ws, int32_t* __restrict__ overflow) {
+  sample_hist_body<false>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, ws, overflow, vq3pick::MaskArgs{}, nullptr);
+}
+
+__global__ __launch_bounds__(256) void sample_hist_masked_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                                 const int64_t* __restrict__ gen, int max_new,
+                                                                 const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                                 int32_t* __restrict__ ws, int32_t* __restrict__ overflow,
+                                                                 vq3pick::MaskArgs m) {
+  __shared__ uint32_t mw[vq3pick::MASK_SLICE_WORDS];
+  sample_hist_body<true>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, ws, overflow, m, mw);
 }
 
 // ------------------------------------------------------------------------------------------------ phase 2: the two cut-offs
@@ -170,12 +214,17 @@ __device__ __forceinline__ void walk_values(unsigned long long mask, const int32
   }
 }
 
+// MASKED: the histogram holds no masked id already; what is left is to keep a penalised id that is masked out of the side values
+// (M: nothing, or one vq3pick::MaskArgs - the unmasked instantiation is the kernel as it always was, argument for argument)
+template <class... M>
 __global__ __launch_bounds__(WALK_THREADS) void sample_walk_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
                                                                    const int64_t* __restrict__ gen, int max_new,
                                                                    const int32_t* __restrict__ step_p, float penalty, int ngram,
                                                                    float temperature, int top_k, float top_p,
                                                                    int32_t* __restrict__ ws, int32_t* __restrict__ overflow,
-                                                                   int32_t* __restrict__ n_kept_out, float* __restrict__ min_kept_out) {
+                                                                   int32_t* __restrict__ n_kept_out, float* __restrict__ min_kept_out,
+                                                                   M... m) {
+  constexpr bool MASKED = sizeof...(M) == 1;
   __shared__ int ov_id[OVL];
   __shared__ float ov_val[OVL];
   __shared__ int ov_n;
@@ -205,7 +254,13 @@ __global__ __launch_bounds__(WALK_THREADS) void sample_walk_kernel(const bf16_t*
   }
   // the row's changed ids, then the finite penalised values among them sorted by value
   int n_pen, n_ov;
-  const bool fits = build_overlay(logits + (long)b * ldl, gen + (long)b * max_new, n, 0, V, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov);
+  bool fits;
+  if constexpr (MASKED)
+    fits = build_overlay(logits + (long)b * ldl, gen + (long)b * max_new, n, 0, V, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov,
+                         RowMask{m..., *step_p - (m.prompt_cols + ...)});
+  else
+    fits = build_overlay(logits + (long)b * ldl, gen + (long)b * max_new, n, 0, V, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov,
+                         NoMask{});
   if (tid == 0) side_n = 0;
   __syncthreads();
   if (fits) {
@@ -323,12 +378,12 @@ __device__ __forceinline__ float gumbel_of(uint32_t r) {
   return -logf(nl);
 }
 
-__global__ __launch_bounds__(256) void sample_draw_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
-                                                          const int64_t* __restrict__ gen, int max_new,
-                                                          const int32_t* __restrict__ step_p, float penalty, int ngram,
-                                                          float temperature, uint32_t seed_lo, uint32_t seed_hi,
-                                                          const int32_t* __restrict__ ws, float* __restrict__ pval,
-                                                          int32_t* __restrict__ pidx, int32_t* __restrict__ overflow) {
+template <bool MASKED>
+__device__ __forceinline__ void sample_draw_body(const bf16_t* __restrict__ logits, long ldl, int V, const int64_t* __restrict__ gen,
+                                                 int max_new, const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                 float temperature, uint32_t seed_lo, uint32_t seed_hi, const int32_t* __restrict__ ws,
+                                                 float* __restrict__ pval, int32_t* __restrict__ pidx, int32_t* __restrict__ overflow,
+                                                 const vq3pick::MaskArgs& m, uint32_t* mw) {
   __shared__ int ov_id[OVL];
   __shared__ float ov_val[OVL];
   __shared__ int ov_n;
@@ -343,7 +398,13 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(const bf16_t* __restri
   int n_pen, n_ov;
   float best = -INFINITY;
   int bi = 0x7fffffff;
-  const bool fits = build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov);
+  bool fits;
+  if constexpr (MASKED) {
+    vq3pick::mask_stage(m, step - m.prompt_cols, c0, c1, mw);        // (build_overlay syncs before it reads)
+    fits = build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov, SliceMask{mw, c0});
+  } else {
+    fits = build_overlay(lg, gen + (long)b * max_new, n, c0, c1, penalty, ngram, ov_id, ov_val, &ov_n, n_pen, n_ov, NoMask{});
+  }
   if (!fits && tid == 0) atomicExch(overflow, 1);
   if (fits && c0 < c1) {
     const float thr = *(const float*)(ws + (long)b * VQ3_SAMPLE_WORK_PER_ROW + THR_SLOT);
@@ -359,6 +420,9 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(const bf16_t* __restri
           float x = bf2f(lg[i]);
           for (int k = 0; k < n_ov; ++k)
             if (ov_id[k] == i) x = ov_val[k];
+          if constexpr (MASKED) {
+            if (vq3pick::mask_bit(mw, c0, i)) x = -INFINITY;
+          }
           if (x >= thr && x < INFINITY) { v[e] = x; any = true; }
         }
       }
@@ -389,23 +453,51 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(const bf16_t* __restri
   }
 }
 
+__global__ __launch_bounds__(256) void sample_draw_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                          const int64_t* __restrict__ gen, int max_new,
+                                                          const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                          float temperature, uint32_t seed_lo, uint32_t seed_hi,
+                                                          const int32_t* __restrict__ ws, float* __restrict__ pval,
+                                                          int32_t* __restrict__ pidx, int32_t* __restrict__ overflow) {
+  sample_draw_body<false>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, temperature, seed_lo, seed_hi, ws, pval, pidx, overflow,
+                          vq3pick::MaskArgs{}, nullptr);
+}
+
+__global__ __launch_bounds__(256) void sample_draw_masked_kernel(const bf16_t* __restrict__ logits, long ldl, int V,
+                                                                 const int64_t* __restrict__ gen, int max_new,
+                                                                 const int32_t* __restrict__ step_p, float penalty, int ngram,
+                                                                 float temperature, uint32_t seed_lo, uint32_t seed_hi,
+                                                                 const int32_t* __restrict__ ws, float* __restrict__ pval,
+                                                                 int32_t* __restrict__ pidx, int32_t* __restrict__ overflow,
+                                                                 vq3pick::MaskArgs m) {
+  __shared__ uint32_t mw[vq3pick::MASK_SLICE_WORDS];
+  sample_draw_body<true>(logits, ldl, V, gen, max_new, step_p, penalty, ngram, temperature, seed_lo, seed_hi, ws, pval, pidx, overflow, m,
+                         mw);
+}
+
 }  // namespace
 
-extern "C" int vq3_sample_pick(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
-                               int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
-                               int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
-                               float temperature, int32_t top_k, float top_p, uint64_t seed, void* sample_work, int32_t* n_kept,
-                               float* min_kept, void* stream) {
-  VQ3_CHECK_ARG(logits_bf16 && work && generated && step && finished && next_ids && sample_work, "sample_pick: null pointer");
-  VQ3_CHECK_ARG(B > 0 && V > 0 && max_new > 0 && ld_logits >= V, "sample_pick: bad shape");
-  VQ3_CHECK_ARG(max_new <= vq3pick::PICK_MAX_IDS, "sample_pick: at most %d ids per row (prompt + new), got %d", vq3pick::PICK_MAX_IDS,
-                max_new);
-  VQ3_CHECK_ARG(repetition_penalty > 0.f, "sample_pick: repetition_penalty must be > 0, got %f", (double)repetition_penalty);
-  VQ3_CHECK_ARG(no_repeat_ngram >= 0 && n_eos >= 0 && (n_eos == 0 || eos_ids), "sample_pick: bad ngram / eos arguments");
-  VQ3_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "sample_pick: temperature must be > 0 and finite, got %f", (double)temperature);
-  VQ3_CHECK_ARG(top_k >= 0, "sample_pick: top_k must be >= 0 (0 = off), got %d", top_k);
-  VQ3_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "sample_pick: top_p must be in (0, 1], got %f", (double)top_p);
-  VQ3_CHECK_ARG(((uintptr_t)sample_work & 15) == 0, "sample_pick: the workspace must be 16-byte aligned");
+// both entries: `mask` NULL is vq3_sample_pick, launch for launch
+static int sample_pick_impl(const char* who, const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V,
+                            int64_t* generated, int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
+                            int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
+                            float temperature, int32_t top_k, float top_p, uint64_t seed, void* sample_work, int32_t* n_kept,
+                            float* min_kept, const vq3_pick_mask* mask, void* stream) {
+  VQ3_CHECK_ARG(logits_bf16 && work && generated && step && finished && next_ids && sample_work, "%s: null pointer", who);
+  VQ3_CHECK_ARG(B > 0 && V > 0 && max_new > 0 && ld_logits >= V, "%s: bad shape", who);
+  VQ3_CHECK_ARG(max_new <= vq3pick::PICK_MAX_IDS, "%s: at most %d ids per row (prompt + new), got %d", who, vq3pick::PICK_MAX_IDS, max_new);
+  VQ3_CHECK_ARG(repetition_penalty > 0.f, "%s: repetition_penalty must be > 0, got %f", who, (double)repetition_penalty);
+  VQ3_CHECK_ARG(no_repeat_ngram >= 0 && n_eos >= 0 && (n_eos == 0 || eos_ids), "%s: bad ngram / eos arguments", who);
+  VQ3_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "%s: temperature must be > 0 and finite, got %f", who, (double)temperature);
+  VQ3_CHECK_ARG(top_k >= 0, "%s: top_k must be >= 0 (0 = off), got %d", who, top_k);
+  VQ3_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0, 1], got %f", who, (double)top_p);
+  VQ3_CHECK_ARG(((uintptr_t)sample_work & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+  if (mask) {
+    const char* bad = vq3pick::mask_args_error(mask->planes, mask->words, mask->min_new, mask->prompt_cols, V);
+    VQ3_CHECK_ARG(bad == nullptr, "%s: %s", who, bad);
+    VQ3_CHECK_ARG((V + PICK_SLICES - 1) / PICK_SLICES <= (vq3pick::MASK_SLICE_WORDS - 2) * 32, "%s: V %d exceeds %d", who, V,
+                  PICK_SLICES * (vq3pick::MASK_SLICE_WORDS - 2) * 32);
+  }
   // work as in vq3_greedy_pick: [B * 64] partial values, [B * 64] partial indices, 1 overflow flag
   float* pval = work;
   int32_t* pidx = (int32_t*)(work + (long)B * PICK_SLICES);
@@ -413,13 +505,45 @@ extern "C" int vq3_sample_pick(const void* logits_bf16, int64_t ld_logits, float
   int32_t* ws = (int32_t*)sample_work;
   const hipStream_t s = (hipStream_t)stream;
   const bf16_t* lg = (const bf16_t*)logits_bf16;
-  hipLaunchKernelGGL(sample_hist_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
-                     repetition_penalty, no_repeat_ngram, ws, overflow);
-  hipLaunchKernelGGL(sample_walk_kernel, dim3(B), dim3(WALK_THREADS), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
-                     repetition_penalty, no_repeat_ngram, temperature, top_k, top_p, ws, overflow, n_kept, min_kept);
-  hipLaunchKernelGGL(sample_draw_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
-                     repetition_penalty, no_repeat_ngram, temperature, (uint32_t)seed, (uint32_t)(seed >> 32), ws, pval, pidx, overflow);
+  if (mask) {
+    const vq3pick::MaskArgs m{mask->planes, mask->words, mask->min_new, mask->prompt_cols};
+    hipLaunchKernelGGL(sample_hist_masked_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, ws, overflow, m);
+    hipLaunchKernelGGL(sample_walk_kernel<vq3pick::MaskArgs>, dim3(B), dim3(WALK_THREADS), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, temperature, top_k, top_p, ws, overflow, n_kept, min_kept, m);
+    hipLaunchKernelGGL(sample_draw_masked_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, temperature, (uint32_t)seed, (uint32_t)(seed >> 32), ws, pval, pidx, overflow,
+                       m);
+  } else {
+    hipLaunchKernelGGL(sample_hist_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, ws, overflow);
+    hipLaunchKernelGGL(sample_walk_kernel<>, dim3(B), dim3(WALK_THREADS), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, temperature, top_k, top_p, ws, overflow, n_kept, min_kept);
+    hipLaunchKernelGGL(sample_draw_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, lg, (long)ld_logits, V, generated, max_new, step,
+                       repetition_penalty, no_repeat_ngram, temperature, (uint32_t)seed, (uint32_t)(seed >> 32), ws, pval, pidx, overflow);
+  }
   vq3pick::launch_pick_final(pval, pidx, generated, max_new, step, finished, eos_ids, n_eos, (long)pad_id, next_ids, B, s);
-  VQ3_CHECK_LAUNCH("sample_pick");
+  VQ3_CHECK_LAUNCH(who);
   return 0;
+}
+
+extern "C" int vq3_sample_pick(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
+                               int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
+                               int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
+                               float temperature, int32_t top_k, float top_p, uint64_t seed, void* sample_work, int32_t* n_kept,
+                               float* min_kept, void* stream) {
+  return sample_pick_impl("sample_pick", logits_bf16, ld_logits, work, B, V, generated, max_new, step, finished, repetition_penalty,
+                          no_repeat_ngram, eos_ids, n_eos, pad_id, next_ids, temperature, top_k, top_p, seed, sample_work, n_kept,
+                          min_kept, nullptr, stream);
+}
+
+extern "C" int vq3_sample_pick_masked(const void* logits_bf16, int64_t ld_logits, float* work, int32_t B, int32_t V, int64_t* generated,
+                                      int32_t max_new, const int32_t* step, int32_t* finished, float repetition_penalty,
+                                      int32_t no_repeat_ngram, const int64_t* eos_ids, int32_t n_eos, int64_t pad_id, int32_t* next_ids,
+                                      float temperature, int32_t top_k, float top_p, uint64_t seed, void* sample_work, int32_t* n_kept,
+                                      float* min_kept, const vq3_pick_mask* mask, void* stream) {
+  VQ3_CHECK_ARG(mask, "sample_pick_masked: null mask");
+  return sample_pick_impl("sample_pick_masked", logits_bf16, ld_logits, work, B, V, generated, max_new, step, finished,
+                          repetition_penalty, no_repeat_ngram, eos_ids, n_eos, pad_id, next_ids, temperature, top_k, top_p, seed,
+                          sample_work, n_kept, min_kept, mask, stream);
 }

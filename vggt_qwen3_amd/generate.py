@@ -155,12 +155,61 @@ def extend(tm, cache: KVCache, inputs_embeds: Optional[torch.Tensor] = None, inp
     return _extend_planned(tm, cache, embeds, plan)
 
 
+def _eos_list(eos_token_id) -> List[int]:
+    return [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+
+
+def _id_list(who: str, name: str, ids, vocab: int) -> List[int]:
+    out = []
+    for t in ([] if ids is None else ids):
+        if isinstance(t, bool) or int(t) != t or not (0 <= int(t) < vocab):
+            raise ValueError(f"{who}: {name} holds {t!r}, not an id in [0, {vocab})")
+        out.append(int(t))
+    return out
+
+
+def _plan_constraints(who: str, vocab: int, max_new_tokens: int, eos_token_id=None, suppress_tokens=None, begin_suppress_tokens=None,
+                      min_new_tokens: int = 0, allowed_token_ids=None, bad_words_ids=None) -> Optional[dict]:
+    """The decoding constraints of a call as the three id sets of ops.mask_planes, host arithmetic only; raises before the GPU is
+    touched. None when no keyword constrains anything (the call then runs the unmasked entries, launch for launch as without them).
+      always    suppress_tokens, one-token bad_words_ids and, with allowed_token_ids, every id outside that set;
+      until_min the eos ids while fewer than min_new_tokens ids are out (nothing without eos_token_id);
+      at_begin  begin_suppress_tokens."""
+    sup = _id_list(who, "suppress_tokens", suppress_tokens, vocab)
+    for entry in ([] if bad_words_ids is None else bad_words_ids):
+        entry = list(entry)
+        if len(entry) != 1:
+            raise NotImplementedError(f"{who}: bad_words_ids entry {entry} has {len(entry)} ids; only one-token entries are supported "
+                                      "(they mean suppress_tokens)")
+        sup += _id_list(who, "bad_words_ids", entry, vocab)
+    begin = _id_list(who, "begin_suppress_tokens", begin_suppress_tokens, vocab)
+    if min_new_tokens is None:
+        min_new_tokens = 0
+    if isinstance(min_new_tokens, bool) or int(min_new_tokens) != min_new_tokens or not (0 <= min_new_tokens <= max_new_tokens):
+        raise ValueError(f"{who}: min_new_tokens must be an integer in 0..max_new_tokens ({max_new_tokens}), got {min_new_tokens}")
+    eos = _id_list(who, "eos_token_id", _eos_list(eos_token_id), vocab) if int(min_new_tokens) > 0 else []
+    always = set(sup)
+    if allowed_token_ids is not None:
+        allowed = set(_id_list(who, "allowed_token_ids", allowed_token_ids, vocab))
+        if not (allowed - always):
+            raise ValueError(f"{who}: allowed_token_ids is empty once the suppressed ids are removed: no id could ever be emitted")
+        always |= set(range(vocab)) - allowed
+    if not always and not begin and not eos:
+        return None
+    return dict(always=sorted(always), until_min=sorted(set(eos)), at_begin=sorted(set(begin)), min_new=int(min_new_tokens) if eos else 0)
+
+
 class DecodeState:
     """Device-resident state of one generate() call."""
 
     def __init__(self, tm, B: int, Lmax: int, gen_cols: int, logprob_cols: int = 0, prompt_cols: int = 0, sampling: bool = False,
-                 kv: Optional[KVCache] = None):
+                 kv: Optional[KVCache] = None, constraints: Optional[dict] = None):
         c, dev = tm.config, tm.flat_w.device
+        # decoding constraints (_plan_constraints): three bit planes over the vocabulary, built once, read by the masked picks
+        self.mask = None
+        if constraints is not None:
+            self.mask = ops.PickMask(ops.mask_planes(tm.vocab, constraints["always"], constraints["until_min"], constraints["at_begin"]),
+                                     constraints["min_new"], prompt_cols, dev)
         self.B, self.Lmax = B, Lmax
         nl = c.num_hidden_layers
         if kv is not None:      # a session's cache: decode on its own K / V and lengths (Lmax is its capacity)
@@ -233,12 +282,16 @@ def _logits_and_pick(tm, st: DecodeState, h: torch.Tensor, opts) -> None:
                       bm["early_stopping"])
         ops.beam_reorder(st.K, st.V, bs.src_row, st.lens, bs.n_prompts, bs.num_beams, bs.all_done)
         return
-    if sm is None:
+    if sm is None and st.mask is None:
         ops.greedy_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
                         opts["pad"], st.next_ids, tm.vocab)
+    elif sm is None:
+        ops.greedy_pick_masked(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
+                               opts["pad"], st.next_ids, tm.vocab, st.mask)
     else:
         ops.sample_pick(logits, st.work, st.generated, st.step, st.finished, opts["penalty"], opts["ngram"], opts["eos"],
-                        opts["pad"], st.next_ids, tm.vocab, sm["temperature"], sm["top_k"], sm["top_p"], sm["seed"], st.sample_work)
+                        opts["pad"], st.next_ids, tm.vocab, sm["temperature"], sm["top_k"], sm["top_p"], sm["seed"], st.sample_work,
+                        mask=st.mask)
     if st.logprobs is not None:     # the raw logits' log-probability of the id just picked, into column step - prompt_cols
         ops.token_logprob_step(logits, tm.vocab, st.next_ids, st.step, st.prompt_cols, st.finished, st.lp_done, st.logprobs, st.lp_work)
 
@@ -287,7 +340,10 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
              num_beams: int = 1, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
              use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False,
-             output_logprobs: bool = False, kv_cache: Optional[KVCache] = None, max_rows: int = 8, **unused):
+             output_logprobs: bool = False, kv_cache: Optional[KVCache] = None, max_rows: int = 8,
+             suppress_tokens: Optional[Sequence[int]] = None, begin_suppress_tokens: Optional[Sequence[int]] = None,
+             min_new_tokens: int = 0, allowed_token_ids: Optional[Sequence[int]] = None,
+             bad_words_ids: Optional[Sequence[Sequence[int]]] = None, **unused):
     """transformers `generate` for the greedy case. With `inputs_embeds` only the NEW tokens are returned (as
     transformers does); with `input_ids` the prompt is prepended and, like transformers, takes part in the repetition
     penalty and n-gram ban. Finished rows emit pad_token_id; generation stops when every row has produced eos or after
@@ -305,14 +361,27 @@ def generate(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: O
     max_rows: the caller's cap on the rows decoded per call, 1..64 (ops.DECODE_MAX_ROWS); more rows than that raise ValueError before
     the GPU is touched. Up to 8 rows a step runs the FMA skinny GEMMs whatever max_rows says; 9..64 rows (bf16 weights, frozen LoRA
     adapters included) run one MFMA weight-streaming GEMM per projection, so a step still streams every weight once. With kv_cache
-    the cache's batch is the row count."""
+    the cache's batch is the row count.
+    Decoding constraints, applied on the device inside the captured step (the masked picks of csrc; a masked id scores -inf exactly as
+    an n-gram-banned one - never picked, and id 0 if a whole row is -inf); they combine with each other and with every keyword above:
+      suppress_tokens        ids that are never emitted (SuppressTokensLogitsProcessor);
+      begin_suppress_tokens  ids that are not emitted as the first new token (SuppressTokensAtBeginLogitsProcessor);
+      min_new_tokens         no eos id before that many new tokens (MinNewTokensLengthLogitsProcessor); nothing without eos_token_id;
+      allowed_token_ids      only these ids are emitted - transformers' prefix_allowed_tokens_fn=lambda b, ids: allowed; put the eos ids
+                             in if rows are to stop; a finished row still emits pad_token_id (pad does not go through the logits);
+      bad_words_ids          one-token entries only, meaning suppress_tokens; a longer entry raises NotImplementedError.
+    An id outside [0, vocab), min_new_tokens outside 0..max_new_tokens or an allowed set that the suppressed ids empty raise ValueError
+    before the GPU is touched. output_logprobs stays the log-probability under the RAW logits. Without any of these keywords the call
+    allocates and launches exactly what it did before they existed."""
     shape_src = inputs_embeds if inputs_embeds is not None else input_ids
     _check_rows("generate", max_rows, 0 if shape_src is None else int(shape_src.shape[0]))
+    constraints = dict(suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
+                       allowed_token_ids=allowed_token_ids, bad_words_ids=bad_words_ids)
     if do_sample or num_beams != 1:
         raise NotImplementedError("generate() is greedy decoding (do_sample=False, num_beams=1) - what the reference's callers use; "
                                   "sample() draws with temperature / top-k / top-p; beam_search() searches with num_beams beams")
     return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1, kv_cache)
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, None, 1, kv_cache, constraints)
 
 
 def _check_rows(who: str, max_rows, n_prompts: int, n_draws: int = 1) -> None:
@@ -343,7 +412,9 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
            no_repeat_ngram_size: int = 0, eos_token_id: Union[int, Sequence[int], None] = None, pad_token_id: Optional[int] = None,
            use_graph: Optional[bool] = None, check_every: int = 8, return_stats: bool = False, output_logprobs: bool = False,
            temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
-           kv_cache: Optional[KVCache] = None, max_rows: int = 8, **unused):
+           kv_cache: Optional[KVCache] = None, max_rows: int = 8, suppress_tokens: Optional[Sequence[int]] = None,
+           begin_suppress_tokens: Optional[Sequence[int]] = None, min_new_tokens: int = 0,
+           allowed_token_ids: Optional[Sequence[int]] = None, bad_words_ids: Optional[Sequence[Sequence[int]]] = None, **unused):
     """transformers `generate(do_sample=True)`: every keyword of generate() above with the same meaning (same processors, same
     eos / pad handling, same return values, output_logprobs included), the pick drawn instead of maximised (vq3_sample_pick, inside
     the captured step like the greedy pick). After the repetition penalty and the n-gram ban, with s = logit / temperature:
@@ -360,25 +431,34 @@ def sample(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Opt
     last hidden state are copied to its n cache rows.
     output_logprobs=True: an entry is log_softmax of the RAW logits at the sampled id (compute_transition_scores on `output_logits`),
     not the probability the id was drawn with after the warpers.
-    kv_cache: as in generate(); with a cache num_return_sequences must be 1 (the cache rows would have to be fanned out)."""
+    kv_cache: as in generate(); with a cache num_return_sequences must be 1 (the cache rows would have to be fanned out).
+    suppress_tokens / begin_suppress_tokens / min_new_tokens / allowed_token_ids / bad_words_ids: as in generate(); here a masked id is
+    never kept and never drawn, and carries no mass in the top-k / top-p cuts."""
     shape_src = inputs_embeds if inputs_embeds is not None else input_ids
     _check_sample_args(temperature, top_k, top_p, num_return_sequences, 0 if shape_src is None else int(shape_src.shape[0]), max_rows)
+    constraints = dict(suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
+                       allowed_token_ids=allowed_token_ids, bad_words_ids=bad_words_ids)
     if seed is None:
         seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
     sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
     return _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, int(num_return_sequences), kv_cache)
+                pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, int(num_return_sequences), kv_cache,
+                constraints)
 
 
 def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-         pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, n_draws, kv_cache=None):
-    """The body of generate() (sampling None, n_draws 1) and sample(): prefill, one eager pick, then the decode steps."""
+         pad_token_id, use_graph, check_every, return_stats, output_logprobs, sampling, n_draws, kv_cache=None, constraints=None):
+    """The body of generate() (sampling None, n_draws 1) and sample(): prefill, one eager pick, then the decode steps. constraints:
+    the five constraint keywords as given (planned here, on the host, before anything touches the GPU)."""
     if kv_cache is not None and n_draws != 1:
         raise ValueError("kv_cache: num_return_sequences must be 1 (fanning a cache row out to several draws is not implemented)")
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if max_new_tokens < 1:
         raise ValueError("max_new_tokens must be >= 1")
+    if constraints is not None:
+        constraints = _plan_constraints("sample" if sampling is not None else "generate", tm.vocab, max_new_tokens, eos_token_id,
+                                        **constraints)
     dev = tm.flat_w.device
     if input_ids is not None:
         input_ids = input_ids.to(dev)
@@ -402,7 +482,7 @@ def _run(tm, inputs_embeds, attention_mask, input_ids, max_new_tokens, repetitio
     n_prompt = L0 if input_ids is not None else 0
     Lmax = round_up(max(n for _, n in spans) + max_new_tokens, 64) if kv_cache is None else kv_cache.capacity
     st = DecodeState(tm, B, Lmax, n_prompt + max_new_tokens, logprob_cols=max_new_tokens if output_logprobs else 0, prompt_cols=n_prompt,
-                     sampling=sampling is not None, kv=kv_cache)
+                     sampling=sampling is not None, kv=kv_cache, constraints=constraints)
     if input_ids is not None:
         st.generated[:, :L0] = input_ids.repeat_interleave(n_draws, dim=0)
         st.step.fill_(L0)
@@ -531,7 +611,8 @@ def beam_search(tm, inputs_embeds: Optional[torch.Tensor] = None, attention_mask
     `sequences_scores` f32; return_stats adds a dict with steps_run, graph, Lmax and the search trace the device recorded: parents /
     tokens i32 and running_scores f32 [steps_run, B * n] - the parent row, last id and score of every running beam after each step -
     and `finished`, the n finished slots of every prompt as the device holds them (sequences i32 [B * n, n_prompt + max_new_tokens],
-    lengths, scores, flags)."""
+    lengths, scores, flags).
+    The decoding constraints of generate() / sample() (suppress_tokens, ...) are not offered here: passing one is a TypeError."""
     shape_src = inputs_embeds if inputs_embeds is not None else input_ids
     eos_list = _check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id,
                                 0 if shape_src is None else int(shape_src.shape[0]))

@@ -842,6 +842,51 @@ def greedy_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids
                                       _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), _stream()), "vq3_greedy_pick")
 
 
+def mask_planes(V: int, always=(), until_min=(), at_begin=()):
+    """The three bit planes of a vq3_pick_mask (include/vq3_hip.h) as numpy uint32 [3, ceil(V / 32)]: bit (id & 31) of word id >> 5 is
+    set in plane 0 for the ids of `always`, in plane 1 for `until_min`, in plane 2 for `at_begin`. Host arithmetic only; an id outside
+    [0, V) raises ValueError."""
+    import numpy as np
+    words = (int(V) + 31) // 32
+    planes = np.zeros((3, words), dtype=np.uint32)
+    for p, ids in enumerate((always, until_min, at_begin)):
+        a = np.asarray(list(ids), dtype=np.int64).reshape(-1)
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= V):
+            raise ValueError(f"mask_planes: ids must lie in [0, {V}), got {int(a.min())} .. {int(a.max())}")
+        np.bitwise_or.at(planes[p], a >> 5, (np.uint32(1) << (a & 31).astype(np.uint32)))
+    return planes
+
+
+class PickMask:
+    """The constraint state of one call on the device (vq3_pick_mask): the planes of mask_planes(), min_new and prompt_cols. The masked
+    entries gate the planes themselves from the device-resident step counter: n_new = *step - prompt_cols."""
+
+    def __init__(self, planes, min_new: int, prompt_cols: int, device):
+        import numpy as np
+        planes = np.ascontiguousarray(planes, dtype=np.uint32)
+        assert planes.ndim == 2 and planes.shape[0] == 3
+        self.words, self.min_new, self.prompt_cols = int(planes.shape[1]), int(min_new), int(prompt_cols)
+        self.planes = torch.from_numpy(planes.view(np.int32).copy()).to(device)
+        self.desc = _lib.PickMask()
+        self.desc.planes, self.desc.words = self.planes.data_ptr(), self.words
+        self.desc.min_new, self.desc.prompt_cols = self.min_new, self.prompt_cols
+
+
+def greedy_pick_masked(logits, work, generated, step, finished, penalty, ngram, eos_ids, pad_id, next_ids, V, mask: PickMask) -> None:
+    """greedy_pick under decoding constraints (vq3_greedy_pick_masked): an id `mask` masks at this step is never picked."""
+    _req(logits, BF16, "pick logits"); _req(work, F32, "pick work"); _req(generated, torch.int64, "pick generated")
+    _req(step, torch.int32, "pick step"); _req(finished, torch.int32, "pick finished"); _req(next_ids, torch.int32, "pick next")
+    B = logits.shape[0]
+    assert logits.stride(1) == 1 and work.numel() >= B * 128 + 1 and generated.is_contiguous() and generated.shape[0] == B
+    assert mask.words * 32 >= V
+    n_eos = 0 if eos_ids is None else int(eos_ids.numel())
+    import ctypes
+    check(_lib.load().vq3_greedy_pick_masked(logits.data_ptr(), logits.stride(0), work.data_ptr(), B, V, generated.data_ptr(),
+                                             generated.shape[1], step.data_ptr(), finished.data_ptr(), float(penalty), int(ngram),
+                                             _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), ctypes.byref(mask.desc), _stream()),
+          "vq3_greedy_pick_masked")
+
+
 SAMPLE_WORK_PER_ROW = 65552     # four-byte slots of vq3_sample_pick's workspace per row (include/vq3_hip.h: VQ3_SAMPLE_WORK_PER_ROW)
 
 
@@ -851,10 +896,12 @@ def sample_workspace(B: int, device) -> torch.Tensor:
 
 
 def sample_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids, pad_id, next_ids, V, temperature, top_k, top_p, seed,
-                sample_work, n_kept: Optional[torch.Tensor] = None, min_kept: Optional[torch.Tensor] = None) -> None:
+                sample_work, n_kept: Optional[torch.Tensor] = None, min_kept: Optional[torch.Tensor] = None,
+                mask: Optional["PickMask"] = None) -> None:
     """greedy_pick's sampling twin (vq3_sample_pick): repetition penalty -> n-gram ban -> temperature -> top-k -> top-p -> a
     Philox / Gumbel-max draw keyed by (seed, *step, row), then the same bookkeeping. sample_work: sample_workspace(B, device);
-    n_kept (i32 [B]) / min_kept (f32 [B]), when given, receive the size of each row's kept set and its smallest kept logit / temperature."""
+    n_kept (i32 [B]) / min_kept (f32 [B]), when given, receive the size of each row's kept set and its smallest kept logit / temperature.
+    mask: decoding constraints (vq3_sample_pick_masked) - a masked id is never kept and carries no mass in the cuts."""
     _req(logits, BF16, "pick logits"); _req(work, F32, "pick work"); _req(generated, torch.int64, "pick generated")
     _req(step, torch.int32, "pick step"); _req(finished, torch.int32, "pick finished"); _req(next_ids, torch.int32, "pick next")
     _req(sample_work, torch.int32, "pick sample_work")
@@ -866,6 +913,15 @@ def sample_pick(logits, work, generated, step, finished, penalty, ngram, eos_ids
     if min_kept is not None:
         _req(min_kept, F32, "pick min_kept"); assert min_kept.is_contiguous() and min_kept.numel() >= B
     n_eos = 0 if eos_ids is None else int(eos_ids.numel())
+    if mask is not None:
+        import ctypes
+        assert mask.words * 32 >= V
+        check(_lib.load().vq3_sample_pick_masked(logits.data_ptr(), logits.stride(0), work.data_ptr(), B, V, generated.data_ptr(),
+                                                 generated.shape[1], step.data_ptr(), finished.data_ptr(), float(penalty), int(ngram),
+                                                 _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), float(temperature), int(top_k),
+                                                 float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, sample_work.data_ptr(), _p(n_kept),
+                                                 _p(min_kept), ctypes.byref(mask.desc), _stream()), "vq3_sample_pick_masked")
+        return
     check(_lib.load().vq3_sample_pick(logits.data_ptr(), logits.stride(0), work.data_ptr(), B, V, generated.data_ptr(),
                                       generated.shape[1], step.data_ptr(), finished.data_ptr(), float(penalty), int(ngram),
                                       _p(eos_ids), n_eos, int(pad_id), next_ids.data_ptr(), float(temperature), int(top_k),

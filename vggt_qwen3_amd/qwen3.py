@@ -384,13 +384,15 @@ class Qwen3ForCausalLM(nn.Module):
             torch.cuda.current_stream().wait_event(ev)       # (the event stays: the VLM's own gate clears both)
 
     def generate(self, *args, **kwargs):
-        """Greedy decoding with a KV cache (vggt_qwen3_amd/generate.py); transformers-compatible keywords."""
+        """Greedy decoding with a KV cache (vggt_qwen3_amd/generate.py); transformers-compatible keywords, the decoding constraints
+        (suppress_tokens, begin_suppress_tokens, min_new_tokens, allowed_token_ids, one-token bad_words_ids) among them."""
         from .generate import generate as _generate
         self._pass_weights_gate()
         return _generate(self, *args, **kwargs)
 
     def sample(self, *args, **kwargs):
-        """Seeded temperature / top-k / top-p decoding with a KV cache, n draws per prompt (vggt_qwen3_amd/generate.py: sample)."""
+        """Seeded temperature / top-k / top-p decoding with a KV cache, n draws per prompt (vggt_qwen3_amd/generate.py: sample); takes
+        generate()'s decoding constraints."""
         from .generate import sample as _sample
         self._pass_weights_gate()
         return _sample(self, *args, **kwargs)
