@@ -107,10 +107,18 @@ __device__ __forceinline__ void for_chunks(int t, int cols, F&& f) {
   }
 }
 
-// Exact-form (erf) GELU, torch.nn.GELU()'s default, two values per VALU instruction: GELU(x) = x * Phi(x) with
-//   Phi(-a) = 2^q(a),  a = min(|x|, 5.5),  q = degree-7 fit of log2 Phi(-a) on [0, 5.5]      (Phi(x) = 1 - Phi(-x) for x > 0)
+// relu(x) for the two GELU forms below, as x - min(x, 0): exact (x - 0 or x - x), a NaN stays a NaN (v_min hands back the 0, NaN - 0 is
+// NaN; v_max(x, 0) alone would drop it) and no finite x overflows ((x + |x|) / 2, the form until now, is inf from x = 2^127 on: the 128
+// largest bf16 values). Two v_min_f32 and one v_pk_add_f32 a pair.
+__device__ __forceinline__ f32x2_t relu2_keep_nan(f32x2_t x) { return x - f32x2_t{fminf(x[0], 0.f), fminf(x[1], 0.f)}; }
+// Exact-form (erf) GELU, torch.nn.GELU()'s default, two values per VALU instruction: GELU(x) = relu(x) - a * Phi(-a) with
+//   Phi(-a) = 2^q(a),  a = min(|x|, 5.5),  q = degree-7 fit of log2 Phi(-a) on [0, 5.5]      (x > 0: x (1 - Phi(-a)) = x - a Phi(-a))
 // log2 Phi(-a) is smooth (it does not saturate as erf does), so 7 packed FMAs + one v_exp_f32 give |error| <= 7e-7 absolute and
-// 1.2e-5 relative for |x| < 3 (Phi of the negative tail is the quantity computed directly, so it keeps its relative accuracy).
+// 1.2e-5 relative for |x| <= 5.5 (the fit is good to 4.3e-6 of Phi(-a); q's seven f32 roundings at |q| <= 26 add at most 3.4e-6).
+// Phi of the negative tail is the quantity that is computed and it is multiplied by a, never added to 0.5: the tail keeps that relative
+// accuracy down to x = -5.5. (Until this form, phi = 0.5 + copysign(0.5 - 2^q, x) rounded Phi(-a) to multiples of 2^-25: 4 % off at
+// x = -5, and x * 2^-25 below -5.5 - unbounded in |x|.) Below -5.5 the result is the constant -5.5 Phi(-5.5) = -1.04e-7 where the
+// function has decayed to 0 (|GELU(x)| < 1.04e-7 there); above 5.5 it is x - 1.04e-7 rounded to f32, which is x itself (half an ulp is 2.4e-7 there).
 // This is the form for f32 results; values that are rounded to bf16 right after take gelu_erf2_b below.
 __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t x) {
   const f32x2_t a = {fminf(fabsf(x[0]), 5.5f), fminf(fabsf(x[1]), 5.5f)};
@@ -122,22 +130,22 @@ __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t x) {
   q = __builtin_elementwise_fma(q, a, f32x2_t{-4.583817849e-01f, -4.583817849e-01f});
   q = __builtin_elementwise_fma(q, a, f32x2_t{-1.151278331e+00f, -1.151278331e+00f});
   q = __builtin_elementwise_fma(q, a, f32x2_t{-9.999938561e-01f, -9.999938561e-01f});
-  const f32x2_t h = {0.5f - __builtin_amdgcn_exp2f(q[0]), 0.5f - __builtin_amdgcn_exp2f(q[1])};
-  const f32x2_t phi = {0.5f + copysignf(h[0], x[0]), 0.5f + copysignf(h[1], x[1])};
-  return x * phi;
+  const f32x2_t e = {__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
+  return __builtin_elementwise_fma(-a, e, relu2_keep_nan(x));
 }
 // The same function for values that are ROUNDED TO BF16 right after (GEMM epilogues with a bf16 output, gelu_fwd): GELU(x) = relu(x) - a * Phi(-a) with
 //   Phi(-a) = 2^q(a),  a = min(|x|, 5.5),  q = degree-5 fit of log2 Phi(-a) on [0, 5.5]      (x > 0: x (1 - Phi(-a)) = x - a Phi(-a))
-// log2 Phi(-a) is smooth (it does not saturate as erf does), so 5 FMAs + one v_exp_f32 give |q error| <= 3.7e-4: GELU within 2.5e-4
-// relative (Phi of the negative tail is the quantity computed directly, so it keeps its relative accuracy) = 0.13 ulp of the bf16 the
-// result is rounded to right after; 3.4e-5 absolute. relu(x) is formed as (x + |x|) / 2 so that a NaN stays a NaN (v_max would drop it).
+// log2 Phi(-a) is smooth (it does not saturate as erf does), so 5 FMAs + one v_exp_f32 give |q error| <= 3.7e-4: GELU within 2.51e-4
+// relative on |x| < 5.5 (Phi of the negative tail is the quantity computed directly, so it keeps its relative accuracy) = 0.064 ulp of
+// the bf16 the result is rounded to right after; 3.4e-5 absolute. Below -5.5 the result is the constant -5.5 Phi(-5.5) = -1.04e-7
+// (|GELU(x)| is smaller than that there: an absolute error of at most 1.04e-7, where torch returns -0).
 // No v_rcp, no log2(e) multiply, none of libm erff's range checks: on the VGGT fc1 GEMM (25 M outputs per launch, one workgroup per
 // CU: nothing overlaps the epilogue) the activation is what the tile's tail costs, and the VALU's ISSUE slots are what it costs in
-// (packed f32 and v_exp_f32 take two each): 11 slots per value here against 14 for the degree-7 form with phi = 0.5 + copysign(0.5 - e, x)
-// (round 2-4; 1.2e-5 relative) and ~30 for the Abramowitz-Stegun 7.1.26 form (v_rcp + v_exp + 12 scalar-lane ops).
+// (packed f32 and v_exp_f32 take two each): 12 slots per value here (11 before relu stopped overflowing) against 13 for the degree-7 form and ~30 for the
+// Abramowitz-Stegun 7.1.26 form (v_rcp + v_exp + 12 scalar-lane ops).
 __device__ __forceinline__ f32x2_t gelu_erf2_b(f32x2_t x) {
-  const f32x2_t ax = {fabsf(x[0]), fabsf(x[1])};
-  const f32x2_t a = {fminf(ax[0], 5.5f), fminf(ax[1], 5.5f)};
+#pragma clang fp contract(off)      // a * 2^q rounds on its own, as it did when the last step was fma(x + |x|, 0.5, -t): the same bits
+  const f32x2_t a = {fminf(fabsf(x[0]), 5.5f), fminf(fabsf(x[1]), 5.5f)};
   f32x2_t q = {-2.3323995992541313e-04f, -2.3323995992541313e-04f};
   q = __builtin_elementwise_fma(q, a, f32x2_t{4.869441967457533e-03f, 4.869441967457533e-03f});
   q = __builtin_elementwise_fma(q, a, f32x2_t{-4.4596340507268906e-02f, -4.4596340507268906e-02f});
@@ -145,7 +153,7 @@ __device__ __forceinline__ f32x2_t gelu_erf2_b(f32x2_t x) {
   q = __builtin_elementwise_fma(q, a, f32x2_t{-1.1462510824203491e+00f, -1.1462510824203491e+00f});
   q = __builtin_elementwise_fma(q, a, f32x2_t{-1.0003620386123657e+00f, -1.0003620386123657e+00f});
   const f32x2_t t = {a[0] * __builtin_amdgcn_exp2f(q[0]), a[1] * __builtin_amdgcn_exp2f(q[1])};
-  return __builtin_elementwise_fma(x + ax, f32x2_t{0.5f, 0.5f}, -t);
+  return relu2_keep_nan(x) - t;
 }
 __device__ __forceinline__ float gelu_erf(float x) { return gelu_erf2(f32x2_t{x, x})[0]; }
 __device__ __forceinline__ float gelu_erf_b(float x) { return gelu_erf2_b(f32x2_t{x, x})[0]; }
